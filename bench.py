@@ -2,7 +2,14 @@
 """Throughput bench of the batched Avalanche vote-record update path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2|c3|c5|c4p|c4pb]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs: it sets up the workload, warms
+up, times the K steps, writes `--dump-outputs` if asked and prints the line
+(metric, value, unit, ms_per_step, ...). `--full` adds everything else described
+below: the delivery, roofline and exchange passes, the secondary workloads, the
+multi-rank replica checks, the CPU baseline and the detail file.
 
 `python bench.py --gpus N` (N > 1) with no launcher around it starts its own N
 rank processes: a fresh `python -m torch.distributed.run` child (before any GPU
@@ -35,7 +42,7 @@ multi-GPU : N ranks split the same network (strong scaling): target shards
          (default: no exchange at all), or node shards with the
          peer-push exchange or an RCCL all-gather (`--shard peers|nodes`).
 
-The line carries the round kernel's roofline: SURVEY.md
+With `--full` the line carries the round kernel's roofline: SURVEY.md
 §8(d)'s algorithmic bytes per launch (9.125 B per live (node, target, round)
 + 20 B per StatusUpdate) over the kernel's HIP-event time, the bytes the
 bit-sliced kernel actually moves, and — from the committed rocprofv3 PMC
@@ -153,7 +160,19 @@ def parse(argv=None):
                          "process's last round-kernel dispatches, tools/pmc_bench.py)")
     ap.add_argument("--detail", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
                     help="where the full per-round / per-workload detail goes (the line stays compact)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure, run everything else the bench measures or checks: the "
+                         "delivery, roofline (HIP-event) and exchange passes, the secondary workloads, the "
+                         "multi-rank replica checks, the CPU baseline, and write the detail file. Without it a "
+                         "run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left for a caller (a seeded "
+                         "sample of the VoteRecords and preferences and of the last segment's pending "
+                         "StatusUpdates, their digest) as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if not args.full:
+        args.no_cpu_baseline = args.no_secondary = args.no_roofline_pass = args.no_exchange_pass = True
+    return args
 
 
 def free_port():
@@ -517,10 +536,70 @@ def log_capacity(n, m, world, rank, shard):
     return min(int(1.25 * n_loc * m_loc) + (1 << 20), (1 << 31) - 1)
 
 
-def measure(wl, args, world, rank, local_rank, steps, warmup):
+DUMP_RUN = 64                # sampled node rows come in runs of 64 consecutive nodes
+DUMP_CELLS = 2_000_000       # sampled (node, target) cells: 16 MB of records + 8 MB of preferences
+DUMP_UPDATES = 500_000       # rows kept of the last segment's StatusUpdates (20 MB)
+DUMP_FETCH_MAX = 1 << 28     # pending updates fetched to the host at most (2 GB of packed words)
+
+
+def dump_outputs(run, path, seed):
+    """--dump-outputs: what the timed path left for its caller after the last timed step, as
+    float64 / float32 .npy files (< 64 MB together), the same from run to run for the same arguments:
+    sample_nodes   [S]        the sampled nodes (seeded runs of DUMP_RUN consecutive nodes)
+    records        [S, M]     av_read_records of those nodes: the packed VoteRecord words
+    preferences    [S, M]     av_read_pref of those nodes: the published IsAccepted bits
+    status_updates [U, 5]     the StatusUpdates the last timed segment left pending, i.e. what the
+                              caller's av_fetch_updates returns after the last step: (round, node, slot,
+                              target, status) in canonical order; a seeded sample above DUMP_UPDATES
+                              rows; not written when the segment emitted none
+    updates_per_round [16]    that stream's updates per round of the epoch (zeros where none)
+    updates_digest [5]        av_updates_digest of that whole stream:
+                              count, sum >> 32, sum & 0xffffffff, xor >> 32, xor & 0xffffffff
+    A rank of a multi-rank run dumps its own shard as <name>_rank<r>.npy."""
+    eng = run.eng
+    rng = np.random.default_rng(seed)
+    eng.synchronize()
+    a, b = eng.node_range
+    m_loc = eng.target_range[1] - eng.target_range[0]
+    runs_all = -(-(b - a) // DUMP_RUN)
+    picks = np.sort(rng.choice(runs_all, size=min(runs_all, max(1, DUMP_CELLS // m_loc // DUMP_RUN)), replace=False))
+    nodes, recs, prefs = [], [], []
+    for p in picks:
+        n0 = a + int(p) * DUMP_RUN
+        n1 = min(n0 + DUMP_RUN, b)
+        nodes.append(np.arange(n0, n1))
+        recs.append(eng.read_records(n0, n1))
+        prefs.append(eng.read_pref(n0, n1))
+    out = {"sample_nodes": np.concatenate(nodes).astype(np.float64),
+           "records": np.concatenate(recs).astype(np.float64),
+           "preferences": np.concatenate(prefs).astype(np.float32)}
+    cnt, sm, xr = eng.updates_digest()
+    out["updates_digest"] = np.array([cnt, sm >> 32, sm & 0xFFFFFFFF, xr >> 32, xr & 0xFFFFFFFF], np.float64)
+    if eng.updates_count() <= DUMP_FETCH_MAX:
+        base, shift = eng.log_base_round(), eng.round_shift
+        words = eng.fetch_updates(decode=False)
+        # a timed segment lies inside one epoch: its first round's place in the epoch is run.pos - rounds
+        first = run.pos - (eng.round - base)
+        per_round = np.bincount((words >> np.uint64(shift)).astype(np.int64) + first % EPOCH, minlength=EPOCH)
+        out["updates_per_round"] = per_round[:EPOCH].astype(np.float64)
+        if words.size > DUMP_UPDATES:
+            words = words[np.sort(rng.choice(words.size, size=DUMP_UPDATES, replace=False))]
+        if words.size:
+            out["status_updates"] = avhip.decode_updates(words, base, shift).astype(np.float64)
+    else:
+        print(f"bench: {eng.updates_count()} pending StatusUpdates: status_updates.npy not written "
+              f"(updates_digest.npy covers them)", file=sys.stderr, flush=True)
+    os.makedirs(path, exist_ok=True)
+    sfx = f"_rank{run.rank}" if run.world > 1 else ""
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + sfx + ".npy"), arr)
+
+
+def measure(wl, args, world, rank, local_rank, steps, warmup, dump=None):
     """This rank's shard of workload `wl`: device warm-up (one untimed epoch),
-    `warmup` untimed steps, `steps` timed steps; then a second pass over the
-    same steps with HIP events around every round kernel (roofline)."""
+    `warmup` untimed steps, `steps` timed steps (then --dump-outputs, if `dump`
+    names a directory); with --full, a second pass over the same steps with HIP
+    events around every round kernel (roofline) and the other passes."""
     n, m, k, init_mode, init_param, byz, replay, desc = WORKLOADS[wl]
     args = argparse.Namespace(**vars(args))  # this workload's copy (its decomposition)
     args.shard = shard_for(wl, world, args.shard)
@@ -531,7 +610,7 @@ def measure(wl, args, world, rank, local_rank, steps, warmup):
     if run.fallback is not None:
         args.shard = "targets"
         args.shard_fallback = run.fallback
-        return measure(wl, args, world, rank, local_rank, steps, warmup)
+        return measure(wl, args, world, rank, local_rank, steps, warmup, dump)
     eng = run.eng
     # ---- device warm-up (untimed): after process start the GPU runs these
     # kernels up to ~15 % slower for the first ~20-30 ms of sustained load
@@ -554,6 +633,9 @@ def measure(wl, args, world, rank, local_rank, steps, warmup):
     # (the timed segments end with the deferred state's write-back, av_materialize: inside the
     # window; the roofline pass below times it on its own as writeback_ms)
     writeback_ms = None
+    if dump:
+        # the engine as the last timed step left it: its state, and the last segment's pending log
+        dump_outputs(run, dump, args.seed)
 
     # ---- delivery (one GPU, sim workloads; detail only): rounds 0-3 of a fresh epoch (the fresh and
     # storm rounds, the most updates) one at a time, each followed by av_fetch_updates of its whole
@@ -675,7 +757,7 @@ def measure(wl, args, world, rank, local_rank, steps, warmup):
         eng.set_option("count_changed", 0)
     replicas = None
     needed_rows = None
-    if world > 1 and args.shard in ("peers", "nodes"):
+    if args.full and world > 1 and args.shard in ("peers", "nodes"):
         # the exchange's own invariant, checked before any resynchronisation: every peer row a local
         # node draws in the next round (R1: the draw is a function of (seed, node, round)) is, in this
         # rank's replica, the row its owner holds now (a push lost in a round shows here)
@@ -979,7 +1061,7 @@ def main(argv=None):
     window = f"{args.warmup}+{args.steps}"
     detail = {"window": window, "n_gpus": world, "workloads": {}}
     try:
-        r = measure(args.workload, args, world, rank, local_rank, args.steps, args.warmup)
+        r = measure(args.workload, args, world, rank, local_rank, args.steps, args.warmup, args.dump_outputs)
         secondary = {}
         if not args.no_secondary:
             if world > 1 and not args.rehearse_one_gpu:
@@ -1054,7 +1136,8 @@ def main(argv=None):
             "writeback_ms": r["writeback_ms"],
             # device memory of the StatusUpdate log (sized for the largest timed segment, size_log)
             "log_gb": r["log_bytes"] / 1e9 if r["log_bytes"] else None,
-            "detail": os.path.relpath(args.detail, ROOT),
+            "full": args.full,
+            "detail": os.path.relpath(args.detail, ROOT) if args.full else None,
         }
         if r["delivery"]:
             line["delivery"] = compact_delivery(r["delivery"])
@@ -1085,9 +1168,10 @@ def main(argv=None):
             detail["cpu_baseline"] = cb
             line["cpu_baseline"] = {k: cb[k] for k in ("value", "unit", "cores", "kind")}
             line["cpu_baseline"]["sample"] = cb["sample_short"]
-        os.makedirs(os.path.dirname(os.path.abspath(args.detail)), exist_ok=True)
-        with open(args.detail, "w") as f:
-            json.dump(detail, f, indent=1)
+        if args.full:
+            os.makedirs(os.path.dirname(os.path.abspath(args.detail)), exist_ok=True)
+            with open(args.detail, "w") as f:
+                json.dump(detail, f, indent=1)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

@@ -1,5 +1,5 @@
 """Generate tests/golden/reference_tests.json — golden vectors transcribed from
-the reference's own tests (/root/reference/avalanche_test.go).
+the reference's own tests (go-avalanche's avalanche_test.go).
 
 Every expected value written here is an assertion of the reference test at the
 cited line, expressed as data (inputs + expected outputs); nothing is computed

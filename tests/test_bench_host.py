@@ -1,10 +1,12 @@
 """bench.py's host logic (no GPU): round kinds of the C4 epoch, the binding
 resource, the roofline built from a roofline pass's per-round rows, the PMC
 summary gate (source digest + window) and the CPU-count rule."""
+import argparse
 import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -208,6 +210,95 @@ def test_size_log_covers_any_single_round():
     e = E()
     bench.size_log(e, per_round, 5, 10)  # window rounds 5..14: no storm round inside
     assert all(v >= int(1.3 * w) for v, w in zip(e.ent, per_round[1]))
+
+
+def test_plain_run_does_the_headline_only_and_full_everything():
+    """Without --full every pass beside the timed steps is off (delivery hangs on the roofline
+    pass); --full runs them as before, each still switchable on its own."""
+    plain = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (plain.steps, plain.warmup, plain.full, plain.dump_outputs) == (7, 2, False, None)
+    assert plain.no_cpu_baseline and plain.no_secondary and plain.no_roofline_pass and plain.no_exchange_pass
+    full = bench.parse(["--full"])
+    assert full.full
+    assert not (full.no_cpu_baseline or full.no_secondary or full.no_roofline_pass or full.no_exchange_pass)
+    part = bench.parse(["--full", "--no-secondary", "--dump-outputs", "out"])
+    assert part.no_secondary and not part.no_roofline_pass and part.dump_outputs == "out"
+
+
+class _DumpEngine:
+    """The engine calls dump_outputs makes, on a 1000 x 40 network whose values name their cell."""
+    node_range, target_range, round, round_shift = (0, 1000), (0, 40), 21, 52
+
+    def __init__(self, per_round):
+        self.per_round = per_round  # pending updates per round 16..20
+
+    def synchronize(self):
+        pass
+
+    def read_records(self, n0, n1):
+        return (np.arange(n0, n1, dtype=np.uint32)[:, None] * 40 + np.arange(40, dtype=np.uint32)) | 0xF0000000
+
+    def read_pref(self, n0, n1):
+        return ((np.arange(n0, n1)[:, None] + np.arange(40)) % 2).astype(np.uint8)
+
+    def updates_count(self):
+        return 5 * self.per_round
+
+    def updates_digest(self):
+        return (5 * self.per_round, (7 << 32) | 9, (0xFFFFFFFF << 32) | 1)
+
+    def log_base_round(self):
+        return 16
+
+    def fetch_updates(self, decode=True):
+        assert not decode
+        rel = np.repeat(np.arange(5, dtype=np.uint64), self.per_round)
+        node = np.tile(np.arange(self.per_round, dtype=np.uint64), 5)
+        return (rel << np.uint64(52)) | (node << np.uint64(28)) | (np.uint64(3) << np.uint64(2)) | np.uint64(2)
+
+
+def test_dump_outputs_files(tmp_path, monkeypatch):
+    """--dump-outputs: float .npy files, the same for the same seed, the sampled nodes' rows
+    exact (record words need float64), the last segment's updates sampled above the row limit."""
+    run = argparse.Namespace(eng=_DumpEngine(300), world=1, rank=0, pos=9)  # the segment: epoch rounds 4..8
+    monkeypatch.setattr(bench, "DUMP_CELLS", 4 * bench.DUMP_RUN * 40)
+    monkeypatch.setattr(bench, "DUMP_UPDATES", 100)
+    bench.dump_outputs(run, str(tmp_path / "a"), 1234)
+    bench.dump_outputs(run, str(tmp_path / "b"), 1234)
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(a) == {"sample_nodes", "records", "preferences", "status_updates", "updates_per_round",
+                      "updates_digest"}
+    for name, arr in a.items():
+        assert arr.dtype in (np.float32, np.float64)
+        assert np.array_equal(arr, np.load(tmp_path / "b" / (name + ".npy")))
+    nodes = a["sample_nodes"].astype(np.int64)
+    assert nodes.size == 4 * bench.DUMP_RUN and np.all(np.diff(nodes) > 0) and nodes.max() < 1000
+    assert np.array_equal(a["records"], ((nodes[:, None] * 40 + np.arange(40)) | 0xF0000000).astype(np.float64))
+    assert np.array_equal(a["preferences"], (nodes[:, None] + np.arange(40)) % 2)
+    su = a["status_updates"]
+    assert su.shape == (100, 5) and np.all(su[:, 3] == 3) and np.all(su[:, 4] == 2)
+    assert set(su[:, 0]) <= {16, 17, 18, 19, 20} and len(set(su[:, 0])) > 1 and su[:, 1].max() < 300
+    assert np.all(np.diff(su[:, 0] * 1000 + su[:, 1]) > 0)  # the sample keeps the canonical order
+    assert a["updates_per_round"].tolist() == [0] * 4 + [300] * 5 + [0] * 7
+    assert a["updates_digest"].tolist() == [1500, 7, 9, 0xFFFFFFFF, 1]
+    # a rank of a multi-rank run names its files after itself; too many pending updates: the digest only
+    run2 = argparse.Namespace(eng=_DumpEngine(10), world=2, rank=1, pos=16)
+    monkeypatch.setattr(bench, "DUMP_FETCH_MAX", 49)
+    bench.dump_outputs(run2, str(tmp_path / "c"), 1234)
+    assert sorted(os.listdir(tmp_path / "c")) == ["preferences_rank1.npy", "records_rank1.npy",
+                                                  "sample_nodes_rank1.npy", "updates_digest_rank1.npy"]
+
+
+def test_dump_outputs_of_a_segment_without_updates(tmp_path):
+    """No file is written empty: a segment that emitted nothing leaves no status_updates.npy, and the
+    per-round counts and the digest say so."""
+    run = argparse.Namespace(eng=_DumpEngine(0), world=1, rank=0, pos=16)
+    bench.dump_outputs(run, str(tmp_path), 1234)
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["preferences.npy", "records.npy", "sample_nodes.npy", "updates_digest.npy",
+                     "updates_per_round.npy"]
+    assert all(np.load(tmp_path / f).size > 0 for f in files)
+    assert np.load(tmp_path / "updates_per_round.npy").tolist() == [0] * 16
 
 
 def test_node_shard_run_length_only_for_conflicting_workloads():

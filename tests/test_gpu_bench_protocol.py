@@ -101,3 +101,46 @@ def test_bench_runner_protocol_vs_oracle(oracle, monkeypatch, wl):
         run.close()
         if state["sim"] is not None:
             state["sim"].close()
+
+
+def test_dump_outputs_are_what_the_last_timed_step_left(oracle, monkeypatch, tmp_path):
+    """bench.py --dump-outputs on measure()'s plain path (3000 x 100 C4-shaped network, steps 0-2 of
+    the epoch after the warm-up epoch: the fresh and two storm rounds): the sampled records and
+    preferences, the segment's StatusUpdates, their per-round counts and digest are the oracle's,
+    bit for bit; a second run writes the same files; the files are float32/float64."""
+    import bench
+    n, m, k = 3000, 100, 8
+    monkeypatch.setitem(bench.WORKLOADS, "c4", (n, m, k, avhip.INIT_BERNOULLI, P80, 0, False, "C4 shape, 3000 x 100"))
+    monkeypatch.setattr(bench, "DUMP_CELLS", 5 * bench.DUMP_RUN * m)  # 5 of the 47 runs of nodes: a real sample
+    args = bench.parse(["--steps", "3", "--warmup", "0"])
+    assert not args.full
+    r = bench.measure("c4", args, 1, 0, 0, args.steps, args.warmup, dump=str(tmp_path / "a"))
+    assert r["applied"] == args.steps * n * m * k and r["kavg_ms"] is None  # no roofline pass in a plain run
+    bench.measure("c4", args, 1, 0, 0, args.steps, args.warmup, dump=str(tmp_path / "b"))
+    got = {}
+    for f in sorted(os.listdir(tmp_path / "a")):
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+        got[f[:-4]] = a
+    assert set(got) == {"sample_nodes", "records", "preferences", "status_updates", "updates_per_round",
+                        "updates_digest"}
+
+    T = _threads()
+    sim = oracle.Sim(n, m, k, seed=args.seed, init_mode=avhip.INIT_BERNOULLI, init_param=P80, threads=T)
+    first = bench.EPOCH  # the timed epoch starts where the warm-up epoch ended
+    sim.set_round_index(first)
+    ups = [sim.run_round(threads=T)[0] for _ in range(args.steps)]
+    nodes = got["sample_nodes"].astype(np.int64)
+    assert nodes.size == 5 * bench.DUMP_RUN and np.all(np.diff(nodes) > 0) and nodes[-1] < n
+    assert np.array_equal(got["records"], sim.dump(threads=T)[nodes])
+    assert np.array_equal(got["preferences"], sim.pref()[nodes])
+    # the timed segment's whole pending stream (below the row limit: not sampled), canonical order
+    assert all(len(x) > 0 for x in ups) and sum(len(x) for x in ups) <= bench.DUMP_UPDATES
+    assert np.array_equal(got["status_updates"], np.concatenate(ups))
+    assert got["updates_per_round"].tolist() == [len(x) for x in ups] + [0] * (bench.EPOCH - args.steps)
+    u = np.concatenate(ups).astype(np.uint64)
+    words = ((u[:, 0] - np.uint64(first)) << np.uint64(52)) | (u[:, 1] << np.uint64(28)) | (u[:, 2] << np.uint64(24)) \
+        | (u[:, 3] << np.uint64(2)) | u[:, 4]
+    cnt, sm, xr = oracle.update_digest(words)
+    assert got["updates_digest"].tolist() == [cnt, sm >> 32, sm & 0xFFFFFFFF, xr >> 32, xr & 0xFFFFFFFF]
+    sim.close()

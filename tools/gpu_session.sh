@@ -61,9 +61,9 @@ for s in "$@"; do
     c2abl) step c2abl 300 bash -c 'for i in 1 2; do for o in "replay_fast=1" "ablate_emit=1"; do echo "== $o"; python tools/fuse_probe.py --fuse 16 --repeat 15 --option $o; done; done' ;;
     ab_matnt) step ab_matnt 600 bash -c 'for i in 1 2 3; do for v in default matnt; do echo "== $v"; if [ $v = default ]; then python tools/wb_probe.py --runs 1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/wb_probe.py --runs 1; fi; done; done' ;;
     probes) step probes 600 bash -c 'for w in c4 c4 c5 c4p; do echo "== $w"; python tools/round_probe.py --workload $w | tail -17; done' ;;
-    benchx2) step bench_a 900 python bench.py && step bench_b 900 python bench.py ;;
+    benchx2) step bench_a 900 python bench.py --full && step bench_b 900 python bench.py --full ;;
     profc4) step profc4 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/profc4 -o c4 -- \
-            python3 bench.py --no-cpu-baseline --no-secondary ;;
+            python3 bench.py --full --no-cpu-baseline --no-secondary ;;
     ab_c3tpw) step ab_c3tpw 600 bash -c 'for i in 1 2; do for t in 4 8 16; do echo "== tpw $t"; python tools/round_probe.py --workload c3 --option tiles_per_wave=$t | tail -1; done; done' ;;
     peers) step pytest_peers 900 python -u -m pytest tests/test_gpu_peer_group.py tests/test_gpu_peer_push.py -x -v -p no:cacheprovider --timeout 300 --timeout-method thread ;;
     gm_c4) step gm_c4 900 python tools/group_model.py --workload c4 --variant nomask:peer_mask=0 --variant tpw16:tiles_per_wave=16 --variant nomask_tpw16:peer_mask=0,tiles_per_wave=16 --json $OUT/group_model_c4.json ;;
@@ -78,30 +78,30 @@ for s in "$@"; do
     ns_probe) step ns_probe 600 bash -c 'for o in "count_changed=0" "count_changed=1"; do python tools/node_shard_probe.py --workload c4p --shards 1,8 --kinds nodes --rounds 6 --option $o; done' ;;
     gm_merge) step gm_merge 900 python tools/group_model.py --workload c4 --kinds targets --target-option uni_merge=4 --json $OUT/group_model_c4_merge4.json ;;
     pmcea_req) step pmcea_req_${WL:-c5} 600 timeout -s KILL 500 rocprofv3 --pmc TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum TCC_EA0_RDREQ_sum \
-            --output-format csv -d $OUT/pmcea_req_${WL:-c5} -o bench -- python3 bench.py --workload ${WL:-c5} --no-cpu-baseline --no-secondary --no-exchange-pass ;;
+            --output-format csv -d $OUT/pmcea_req_${WL:-c5} -o bench -- python3 bench.py --full --workload ${WL:-c5} --no-cpu-baseline --no-secondary --no-exchange-pass ;;
     pmcea_dram) step pmcea_dram_${WL:-c5} 600 timeout -s KILL 500 rocprofv3 --pmc TCC_EA0_RDREQ_DRAM_sum TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum GRBM_GUI_ACTIVE \
-            --output-format csv -d $OUT/pmcea_dram_${WL:-c5} -o bench -- python3 bench.py --workload ${WL:-c5} --no-cpu-baseline --no-secondary --no-exchange-pass ;;
+            --output-format csv -d $OUT/pmcea_dram_${WL:-c5} -o bench -- python3 bench.py --full --workload ${WL:-c5} --no-cpu-baseline --no-secondary --no-exchange-pass ;;
     pmcea_sum) step pmcea_sum_${WL:-c5} 120 python tools/pmc_ea.py --req $OUT/pmcea_req_${WL:-c5} --dram $OUT/pmcea_dram_${WL:-c5} --out $OUT/pmc_ea_${WL:-c5}.json ;;
     pmclist) step pmclist 120 rocprofv3 -L ;;
     testsall) step pytest_gpu 1500 python -m pytest tests -m gpu -q -p no:cacheprovider ;;
-    bench) step bench 900 python bench.py ;;
+    bench) step bench 900 python bench.py --full ;;
     rccl2) step rccl2 240 python tools/rccl_two_rank_probe.py ;;
     rehearse2) step rehearse2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-            --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 2 --rehearse-one-gpu --no-secondary ;;
+            --master-addr 127.0.0.1 --master-port 29531 bench.py --full --gpus 2 --rehearse-one-gpu --no-secondary ;;
     rehearse4) step rehearse4 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 \
-            --master-addr 127.0.0.1 --master-port 29532 bench.py --gpus 4 --rehearse-one-gpu --no-secondary ;;
+            --master-addr 127.0.0.1 --master-port 29532 bench.py --full --gpus 4 --rehearse-one-gpu --no-secondary ;;
     rehearse2p) step rehearse2p 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-            --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --rehearse-one-gpu --no-secondary --shard peers ;;
+            --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --rehearse-one-gpu --no-secondary --shard peers ;;
     rehearse2s) step rehearse2s 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-            --master-addr 127.0.0.1 --master-port 29535 bench.py --gpus 2 --rehearse-one-gpu --shard peers ;;
+            --master-addr 127.0.0.1 --master-port 29535 bench.py --full --gpus 2 --rehearse-one-gpu --shard peers ;;
     rehearse8p) step rehearse8p 420 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-            --master-addr 127.0.0.1 --master-port 29538 bench.py --gpus 8 --rehearse-one-gpu --no-secondary --workload c4p ;;
+            --master-addr 127.0.0.1 --master-port 29538 bench.py --full --gpus 8 --rehearse-one-gpu --no-secondary --workload c4p ;;
     rehearse8) step rehearse8 420 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-            --master-addr 127.0.0.1 --master-port 29539 bench.py --gpus 8 --rehearse-one-gpu --no-secondary ;;
+            --master-addr 127.0.0.1 --master-port 29539 bench.py --full --gpus 8 --rehearse-one-gpu --no-secondary ;;
     rehearse8all) step rehearse8all 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-            --master-addr 127.0.0.1 --master-port 29540 bench.py --gpus 8 --rehearse-one-gpu ;;
+            --master-addr 127.0.0.1 --master-port 29540 bench.py --full --gpus 8 --rehearse-one-gpu ;;
     rehearse4p) step rehearse4p 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 \
-            --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 4 --rehearse-one-gpu --no-secondary --shard peers ;;
+            --master-addr 127.0.0.1 --master-port 29534 bench.py --full --gpus 4 --rehearse-one-gpu --no-secondary --shard peers ;;
     capped) step capped 600 python -u -m pytest tests/test_gpu_parity.py -x -v -p no:cacheprovider --timeout 300 --timeout-method thread -k "capped or c2 or replay or fuzz or poll_sets" ;;
     fresh) step fresh 600 python -u -m pytest tests/test_gpu_fresh.py tests/test_gpu_count_lazy.py tests/test_gpu_virtual_votes.py tests/test_gpu_parity.py -x -v -p no:cacheprovider --timeout 300 --timeout-method thread ;;
     probe_c4) step probe_c4 300 python tools/round_probe.py --workload c4 --json $OUT/probe_c4.json ;;
@@ -138,24 +138,24 @@ for s in "$@"; do
     conv_c3) step conv_c3 900 python tools/run_to_finalization.py --workload c3 --json $OUT/conv_c3.json ;;
     conv_c5) step conv_c5 900 python tools/run_to_finalization.py --workload c5 --max-rounds 64 --json $OUT/conv_c5.json ;;
     conv_c4) step conv_c4 900 python tools/run_to_finalization.py --workload c4 --max-rounds 64 --json $OUT/conv_c4.json ;;
-    bench_c2) step bench_c2 900 python bench.py --workload c2 --no-cpu-baseline ;;
-    bench_c2v1) step bench_c2v1 900 python bench.py --workload c2 --no-cpu-baseline --kernel 1 ;;
-    bench_c3) step bench_c3 900 python bench.py --workload c3 --no-cpu-baseline ;;
-    bench_c5) step bench_c5 900 python bench.py --workload c5 --no-cpu-baseline ;;
+    bench_c2) step bench_c2 900 python bench.py --full --workload c2 --no-cpu-baseline ;;
+    bench_c2v1) step bench_c2v1 900 python bench.py --full --workload c2 --no-cpu-baseline --kernel 1 ;;
+    bench_c3) step bench_c3 900 python bench.py --full --workload c3 --no-cpu-baseline ;;
+    bench_c5) step bench_c5 900 python bench.py --full --workload c5 --no-cpu-baseline ;;
     prof) step prof 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- \
-            python3 bench.py --no-cpu-baseline ;;
+            python3 bench.py --full --no-cpu-baseline ;;
     pmcb_sq) step pmcb_sq_${WL:-c4} 600 timeout -s KILL 500 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_WAVES SQ_WAIT_ANY SQ_WAVE_CYCLES GRBM_GUI_ACTIVE \
-            --output-format csv -d $OUT/pmcb_sq_${WL:-c4} -o bench -- python3 bench.py --workload ${WL:-c4} --no-cpu-baseline --no-secondary --no-exchange-pass ;;
+            --output-format csv -d $OUT/pmcb_sq_${WL:-c4} -o bench -- python3 bench.py --full --workload ${WL:-c4} --no-cpu-baseline --no-secondary --no-exchange-pass ;;
     pmcb_fetch) step pmcb_fetch_${WL:-c4} 600 timeout -s KILL 500 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmcb_fetch_${WL:-c4} -o bench -- \
-            python3 bench.py --workload ${WL:-c4} --no-cpu-baseline --no-secondary --no-exchange-pass ;;
+            python3 bench.py --full --workload ${WL:-c4} --no-cpu-baseline --no-secondary --no-exchange-pass ;;
     pmcb_write) step pmcb_write_${WL:-c4} 600 timeout -s KILL 500 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmcb_write_${WL:-c4} -o bench -- \
-            python3 bench.py --workload ${WL:-c4} --no-cpu-baseline --no-secondary --no-exchange-pass ;;
+            python3 bench.py --full --workload ${WL:-c4} --no-cpu-baseline --no-secondary --no-exchange-pass ;;
     pmcb_sum) step pmcb_sum_${WL:-c4} 300 python tools/pmc_bench.py --workload ${WL:-c4} --sq $OUT/pmcb_sq_${WL:-c4} --fetch $OUT/pmcb_fetch_${WL:-c4} \
             --write $OUT/pmcb_write_${WL:-c4} --calib-fetch $OUT/calib_fetch --calib-write $OUT/calib_write ${PMC_LAUNCHES:+--launches $PMC_LAUNCHES} ${PMC_REPLAY:+--replay} --out $OUT/pmc_${WL:-c4}.json ;;
     pmc_fetch) step pmc_fetch 900 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o bench -- \
-            python3 bench.py --no-cpu-baseline --no-secondary --no-exchange-pass ;;
+            python3 bench.py --full --no-cpu-baseline --no-secondary --no-exchange-pass ;;
     pmc_write) step pmc_write 900 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o bench -- \
-            python3 bench.py --no-cpu-baseline --no-secondary --no-exchange-pass ;;
+            python3 bench.py --full --no-cpu-baseline --no-secondary --no-exchange-pass ;;
     calib_fetch) step calib_fetch 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/calib_fetch -o calib -- \
             go-avalanche_amd/bin/pmc_calib ;;
     calib_write) step calib_write 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/calib_write -o calib -- \
@@ -181,7 +181,7 @@ for s in "$@"; do
     gaps_ef) step gaps_ef 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/gaps_ef -o gap -- python3 tools/gap_probe.py --workload c4 --events-first ;;
     gaps2) step gaps2 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/gaps2 -o gap -- python3 tools/gap_probe.py --workload c2 ;;
     profc2) step profc2 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/profc2 -o c2 -- \
-            python3 bench.py --workload c2 --no-cpu-baseline ;;
+            python3 bench.py --full --workload c2 --no-cpu-baseline ;;
     probe_c2abl) step probe_c2abl 600 bash -c 'for o in "replay_prefetch=0" "replay_prefetch=1" "ablate_node=1" "ablate_node=2" "ablate_node=4" "ablate_emit=1" "ablate_emit=1 --option ablate_node=7"; do echo "== $o"; python tools/round_probe.py --workload c2 --option $o | tail -2; done' ;;
     profc2p) step profc2p 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/profc2p -o c2 -- \
             python3 tools/round_probe.py --workload c2 ;;
@@ -192,12 +192,12 @@ for s in "$@"; do
     probe_ref) step probe_ref 300 bash -c 'for o in "ref_rows=1" "ref_rows=0"; do echo "== $o"; python tools/round_probe.py --workload c4 --option $o; done' ;;
     nstpw) step nstpw 600 bash -c 'for o in "tiles_per_wave=4" "tiles_per_wave=2" "tiles_per_wave=1"; do python tools/node_shard_probe.py --shards 1,2,4,8 --kinds nodes --option $o; done' ;;
     probe_settled) step probe_settled 600 bash -c 'for o in "ablate_settled=0" "ablate_settled=1" "ablate_settled=2" "ablate_settled=4" "ablate_settled=8" "ablate_settled=15" "ablate_settled=7"; do echo "== $o"; python tools/round_probe.py --workload c4 --option $o | grep "\"round\": 1[0-2],"; done' ;;
-    benchwin) step benchwin 900 bash -c 'python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-secondary && python bench.py --steps 5 --warmup 0 --no-cpu-baseline --no-secondary && python bench.py --steps 100 --warmup 3 --no-cpu-baseline --no-secondary' ;;
+    benchwin) step benchwin 900 bash -c 'python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-secondary && python bench.py --full --steps 5 --warmup 0 --no-cpu-baseline --no-secondary && python bench.py --full --steps 100 --warmup 3 --no-cpu-baseline --no-secondary' ;;
     probe_tpw) step probe_tpw 600 bash -c 'for w in c4 c3; do for o in "tiles_per_wave=4" "tiles_per_wave=6" "tiles_per_wave=8" "tiles_per_wave=3"; do echo "== $w $o"; python tools/round_probe.py --workload $w --option $o | tail -1 | grep -o "kernel_ms_total.*"; done; done' ;;
     c4ptests) step c4ptests 900 python -u -m pytest tests/test_gpu_fullsize.py -x -v -s -p no:cacheprovider --timeout 600 --timeout-method thread -k "c4p" ;;
     hostcpu) step hostcpu 300 bash -c 'cat /sys/fs/cgroup/cpu.max; nproc; python -c "import bench, json; print(json.dumps(bench.host_cpus()))"; for t in 16 32 64 128; do python tools/cpu_scaling.py --threads $t; done' ;;
-    bench_c4p) step bench_c4p 900 python bench.py --workload c4p --no-cpu-baseline --no-secondary --no-exchange-pass ;;
-    bench_c4pb) step bench_c4pb 900 python bench.py --workload c4pb --no-cpu-baseline --no-secondary --no-exchange-pass ;;
+    bench_c4p) step bench_c4p 900 python bench.py --full --workload c4p --no-cpu-baseline --no-secondary --no-exchange-pass ;;
+    bench_c4pb) step bench_c4pb 900 python bench.py --full --workload c4pb --no-cpu-baseline --no-secondary --no-exchange-pass ;;
     probe_lean) step probe_lean 600 bash -c 'for w in c4 c5; do for o in "settled_lean=1" "settled_lean=0"; do echo "== $w $o"; python tools/round_probe.py --workload $w --option $o; done; done' ;;
     fullc4) step fullc4 900 python -u -m pytest tests/test_gpu_fullsize.py -x -v -s -p no:cacheprovider --timeout 600 --timeout-method thread -k "c4_fullsize" ;;
     probe_ref2) step probe_ref2 600 bash -c 'for w in c4 c5; do for o in "ref_rows=1" "ref_rows=0"; do echo "== $w $o"; python tools/round_probe.py --workload $w --option $o; done; done' ;;
@@ -228,9 +228,9 @@ for s in "$@"; do
     uvtests) step uvtests 900 python -u -m pytest tests/test_gpu_uniform_rows.py tests/test_gpu_bench_protocol.py tests/test_gpu_count_lazy.py tests/test_gpu_virtual_votes.py tests/test_gpu_fullsize.py -k "uniform or uni_ or protocol or lazy or virtual or c4_fullsize or c5_whole" -x -v -p no:cacheprovider --timeout 600 --timeout-method thread ;;
     pmcall) for W in c4 c4p c4pb c3 c5; do WL=$W bash "$0" pmcb_sq pmcb_fetch pmcb_write pmcb_sum || exit $?; done
             WL=c2 PMC_LAUNCHES=2 PMC_REPLAY=1 bash "$0" pmcb_sq pmcb_fetch pmcb_write pmcb_sum || exit $? ;;
-    bench4) step bench 900 python bench.py --detail gpurun_out/bench_detail.json ;;
-    self2) step self2 600 python bench.py --gpus 2 --rehearse-one-gpu --no-secondary --detail gpurun_out/rehearse2_detail.json ;;
-    self2s) step self2s 900 python bench.py --gpus 2 --rehearse-one-gpu --detail gpurun_out/rehearse2s_detail.json ;;
+    bench4) step bench 900 python bench.py --full --detail $OUT/bench_detail.json ;;
+    self2) step self2 600 python bench.py --full --gpus 2 --rehearse-one-gpu --no-secondary --detail $OUT/rehearse2_detail.json ;;
+    self2s) step self2s 900 python bench.py --full --gpus 2 --rehearse-one-gpu --detail $OUT/rehearse2s_detail.json ;;
     exchcost) step exchcost 300 python tools/exchange_cost.py --json gpurun_out/exchange_cost.json ;;
     barrier4) step barrier4 400 bash -c 'python tools/barrier_cost.py --world 2 --json gpurun_out/barrier2_small.json && python tools/barrier_cost.py --world 2 --nodes 131072 --json gpurun_out/barrier2_big.json && python tools/barrier_cost.py --world 4 --nodes 131072 --json gpurun_out/barrier4_big.json && python tools/barrier_cost.py --world 2 --nodes 1000000 --rounds 40 --json gpurun_out/barrier2_c4.json' ;;
     abr3) step abr3 600 bash -c 'for w in c4 c4p c4pb; do for v in new nohoist r3; do echo "== $w $v"; if [ $v = new ]; then python tools/round_probe.py --workload $w | tail -1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w | tail -1; fi; done; done; for v in new r3; do echo "== c2 $v"; if [ $v = new ]; then python tools/fuse_probe.py; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/fuse_probe.py; fi; done' ;;
@@ -251,20 +251,20 @@ for s in "$@"; do
     abpad) step abpad 900 bash -c 'for w in c4p c4 c4pb c4p; do for v in new pad; do echo "== $w $v"; if [ $v = new ]; then python tools/round_probe.py --workload $w | tail -1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w | tail -1; fi; done; done; for o in 2 3; do echo "== c4p pad ablate_emit=$o"; AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_pad.so python tools/round_probe.py --workload c4p --option ablate_emit=$o | tail -1; done; for v in new pad; do echo "== c2 $v"; if [ $v = new ]; then python tools/fuse_probe.py; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/fuse_probe.py; fi; done' ;;
     quicktwo) step quicktwo 900 env AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_two.so python -u -m pytest tests/test_gpu_peer_push.py tests/test_gpu_parity.py tests/test_gpu_uniform_rows.py tests/test_gpu_count_lazy.py tests/test_gpu_virtual_votes.py tests/test_gpu_fresh.py tests/test_gpu_replay_fused.py -x -q -p no:cacheprovider --timeout 300 --timeout-method thread ;;
     abtwo) step abtwo 900 bash -c 'for w in c4p c4pb c4 c4p; do for v in pad two; do echo "== $w $v"; AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w | tail -1; done; done; for v in pad two; do echo "== c2 $v"; AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/fuse_probe.py; done' ;;
-    profc4) step profc4 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/profc4 -o c4 -- python3 bench.py --no-cpu-baseline --no-secondary ;;
+    profc4) step profc4 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/profc4 -o c4 -- python3 bench.py --full --no-cpu-baseline --no-secondary ;;
     ablognt) step ablognt 600 bash -c 'for w in c4p c4 c4pb c4p; do for v in new lognt; do echo "== $w $v"; if [ $v = new ]; then python tools/round_probe.py --workload $w | tail -1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w | tail -1; fi; done; done' ;;
     abpub) step abpub 600 bash -c 'for w in c4p c4 c4pb c4p; do for v in new pubplain sp3; do echo "== $w $v"; if [ $v = new ]; then python tools/round_probe.py --workload $w | tail -1; elif [ $v = sp3 ]; then python tools/round_probe.py --workload $w --option store_policy=3 | tail -1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w | tail -1; fi; done; done' ;;
     abwpe) step abwpe 600 bash -c 'for w in c4p c4 c4pb c4p c4; do for v in new w5 w7; do echo "== $w $v"; if [ $v = new ]; then python tools/round_probe.py --workload $w | tail -1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w | tail -1; fi; done; done' ;;
     abwpe2) step abwpe2 600 bash -c 'for w in c4p c4 c4pb c4p c4 c5 c3; do for v in new w5 w4; do echo "== $w $v"; if [ $v = new ]; then python tools/round_probe.py --workload $w | tail -1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w | tail -1; fi; done; done' ;;
     abf5) step abf5 600 bash -c 'for w in c4 c4p c4 c4p c4pb c5; do for v in w5 f5; do echo "== $w $v"; AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w > gpurun_out/rp_tmp.txt 2>/dev/null; head -1 gpurun_out/rp_tmp.txt; tail -1 gpurun_out/rp_tmp.txt; done; done' ;;
-    self4s) step self4s 900 python bench.py --gpus 4 --rehearse-one-gpu --detail gpurun_out/rehearse4s_detail.json ;;
+    self4s) step self4s 900 python bench.py --full --gpus 4 --rehearse-one-gpu --detail $OUT/rehearse4s_detail.json ;;
     abrun8) step abrun8 600 bash -c 'for w in c4 c4p c4 c4p c4pb; do for o in "tiles_per_wave=0 --option uni_merge=1" "tiles_per_wave=8 --option uni_merge=2" "tiles_per_wave=4 --option uni_merge=4"; do echo "== $w $o"; python tools/round_probe.py --workload $w --option $o | tail -1; done; done' ;;
     abc5tpw) step abc5tpw 600 bash -c 'for w in c5 c5; do for o in 0 4 16; do echo "== $w tpw=$o"; python tools/round_probe.py --workload $w --option tiles_per_wave=$o | tail -1; done; done' ;;
     c2ab) step c2ab 300 bash -c 'for v in new s3; do echo "== c2 $v"; if [ $v = new ]; then python tools/fuse_probe.py; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/fuse_probe.py; fi; done' ;;
-    reh2pb) step reh2pb 600 python bench.py --gpus 2 --rehearse-one-gpu --workload c4pb --shard peers --no-secondary --detail gpurun_out/rehearse2_c4pb_detail.json ;;
-    reh2t) step reh2t 600 python bench.py --gpus 2 --rehearse-one-gpu --shard targets --no-secondary --detail gpurun_out/rehearse2_targets_detail.json ;;
+    reh2pb) step reh2pb 600 python bench.py --full --gpus 2 --rehearse-one-gpu --workload c4pb --shard peers --no-secondary --detail $OUT/rehearse2_c4pb_detail.json ;;
+    reh2t) step reh2t 600 python bench.py --full --gpus 2 --rehearse-one-gpu --shard targets --no-secondary --detail $OUT/rehearse2_targets_detail.json ;;
     abs3) step abs3 900 bash -c 'for w in c4 c4p c4pb c3; do for v in new s3; do for cc in 0 1; do echo "== $w $v count_changed=$cc"; if [ $v = new ]; then python tools/round_probe.py --workload $w --option count_changed=$cc | tail -1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w --option count_changed=$cc | tail -1; fi; done; done; done; for v in new s3; do echo "== c2 $v"; if [ $v = new ]; then python tools/fuse_probe.py; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/fuse_probe.py; fi; done' ;;
-    profc2b) step profc2b 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/profc2b -o c2 -- python3 bench.py --workload c2 --no-cpu-baseline --no-secondary ;;
+    profc2b) step profc2b 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/profc2b -o c2 -- python3 bench.py --full --workload c2 --no-cpu-baseline --no-secondary ;;
     abcc) step abcc 600 bash -c 'for w in c4 c4p; do for v in new noccpf; do for cc in 0 1; do echo "== $w $v count_changed=$cc"; if [ $v = new ]; then python tools/round_probe.py --workload $w --option count_changed=$cc | tail -1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w --option count_changed=$cc | tail -1; fi; done; done; done; python tools/round_probe.py --workload c4pb | tail -1' ;;
     shardmodel) step shardmodel 600 bash -c 'python tools/shard_model.py --workload c4 --json gpurun_out/shard_model_c4.json && python tools/shard_model.py --workload c4p --json gpurun_out/shard_model_c4p.json' ;;
     fused4) step fused4 600 python -u -m pytest tests/test_gpu_replay_fused.py tests/test_gpu_parity.py -x -v -p no:cacheprovider --timeout 300 --timeout-method thread ;;

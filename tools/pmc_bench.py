@@ -9,7 +9,7 @@ as the timed steps, each bracketed by HIP events. The roofline pass is the
 last `steps` round-kernel dispatches of the process (run with --no-secondary),
 so this averages the counters over exactly those dispatches.
 
-Inputs are rocprofv3 --pmc passes of `python3 bench.py --workload W
+Inputs are rocprofv3 --pmc passes of `python3 bench.py --full --workload W
 --no-cpu-baseline --no-secondary --no-exchange-pass --steps S --warmup W` (one pass per counter
 group, MI355X_MICROARCH.md §HBM / the 8-SQ-counter limit):
   --sq    SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR

@@ -6,7 +6,7 @@ the bytes they stand for, and the share of requests that go on to DRAM (the
 rest are Infinity-Cache hits). Attributes a workload's fabric bytes beyond the
 kernel's byte model (C5 moved 1.6x its model).
 
-Inputs: rocprofv3 --pmc passes of `python3 bench.py --workload W --no-cpu-baseline
+Inputs: rocprofv3 --pmc passes of `python3 bench.py --full --workload W --no-cpu-baseline
 --no-secondary --no-exchange-pass`:
   --req  TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum TCC_EA0_RDREQ_sum
   --dram TCC_EA0_RDREQ_DRAM_sum TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum GRBM_GUI_ACTIVE

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The headline workload's roofline-pass dispatches in a rocprofv3 kernel trace of `python bench.py`
+"""The headline workload's roofline-pass dispatches in a rocprofv3 kernel trace of `python bench.py --full`
 (`--kernel-trace --output-format csv`): the bench runs the headline first, and its roofline pass is
 the `launches` sweep-round dispatches before the last write-back (`k_materialize`) that precedes its
 exchange pass, whose warm rounds are the first dispatches of the counting kernel build
