@@ -242,6 +242,7 @@ struct av_engine {
   uint32_t push_store = 1;         // option "push_store" (RoundParams::push_store)
   uint32_t tile_draw = 0;          // option "tile_draw" (RoundParams::tile_draw, A/B)
   uint32_t mat_run = 1;            // option "materialize_run" (RoundParams::mat_run, A/B)
+  uint32_t census_blocks = 0;      // option "census_blocks": workgroups of av_census's grid (0 = the engine's choice)
   bool masked = false;             // set up by the exchange's initialisation (mask_setup)
   uint32_t segs = 1;               // 32-word segments per row
   uint8_t* need_mine = nullptr;    // [kNeedWin][N]: rows this rank's nodes draw in a window's rounds
@@ -2448,6 +2449,69 @@ int av_live_records(av_engine* e, int32_t honest_only, int64_t* out) {
   return AV_OK;
 }
 
+// IsAccepted / GetConfidence over every Processor (processor.go:125-140) and the example's stop test
+// (main.go:143-162: a node is done when it holds no live record), tallied on the device: one pass
+// over the A and K planes (census.hip), read through the deferred count forms like av_read_records
+// and, like it, leaving them in place.
+int av_census(av_engine* e, int64_t n0, int64_t n1, int32_t honest_only, const av_census_out* out) {
+  AV_ENTER(e);
+  AV_PEER_SYNC_CHECK(e);
+  AV_CHECK(out && (out->target_classes || out->target_count_sum || out->node_classes || out->count_hist),
+           AV_ERR_INVALID_ARG, "no census output requested");
+  AV_CHECK(n0 >= e->n0 && n0 <= n1 && n1 <= e->n1, AV_ERR_INVALID_ARG, "range outside this engine's shard");
+  const size_t tn = (size_t)(e->t1 - e->t0), nn = (size_t)(n1 - n0);
+  if (out->target_classes) std::fill(out->target_classes, out->target_classes + tn * AV_CENSUS_CLASSES, (int64_t)0);
+  if (out->target_count_sum) std::fill(out->target_count_sum, out->target_count_sum + tn, (int64_t)0);
+  if (out->node_classes) std::fill(out->node_classes, out->node_classes + nn * AV_CENSUS_CLASSES, (int32_t)0);
+  if (out->count_hist) std::fill(out->count_hist, out->count_hist + 256, (int64_t)0);
+  if (!nn || !tn) return AV_OK;
+  // device sums: [tn][3] classes (live rejected, live accepted, absent accepted), [tn] count sums,
+  // [256] histogram, the nodes counted, one pad word; then the node rows (16-byte aligned)
+  const size_t head = tn * 4 + 256 + 2, head_bytes = head * 8;
+  void* buf = nullptr;
+  int rc = engine_scratch(e, head_bytes + (out->node_classes ? nn * 16 : 0), &buf);
+  if (rc != AV_OK) return rc;
+  AV_HIP(hipMemsetAsync(buf, 0, head_bytes + (out->node_classes ? nn * 16 : 0), e->stream));
+  auto* d = static_cast<unsigned long long*>(buf);
+  avk::CensusParams p{};
+  p.planes = e->planes;
+  p.kpend = e->k_pend ? e->kpend : nullptr;
+  p.valid = e->valid;
+  p.byz = e->byz;
+  p.tcls = out->target_classes ? d : nullptr;
+  p.tsum = out->target_count_sum ? d + tn * 3 : nullptr;
+  p.hist = out->count_hist ? d + tn * 4 : nullptr;
+  p.counted = d + tn * 4 + 256;
+  p.ncls = out->node_classes ? reinterpret_cast<int32_t*>(d + head) : nullptr;
+  p.BL = e->BL;
+  p.tn = (uint32_t)tn;
+  p.n0 = (uint32_t)e->n0;
+  p.honest_only = honest_only ? 1u : 0u;
+  AV_HIP(avk::launch_census(p, (uint32_t)(n0 - e->n0), (uint32_t)(n1 - e->n0), e->census_blocks, e->stream));
+  std::vector<unsigned long long> h(head);
+  AV_HIP(hipMemcpyAsync(h.data(), d, head_bytes, hipMemcpyDeviceToHost, e->stream));
+  if (out->node_classes)
+    AV_HIP(hipMemcpyAsync(out->node_classes, d + head, nn * 16, hipMemcpyDeviceToHost, e->stream));
+  AV_HIP(hipStreamSynchronize(e->stream));
+  AV_PEER_CHECK(e);
+  if (out->target_classes) {
+    const int64_t counted = (int64_t)h[tn * 4 + 256];
+    for (size_t t = 0; t < tn; ++t) {
+      int64_t* row = out->target_classes + t * AV_CENSUS_CLASSES;
+      row[AV_CENSUS_LIVE_REJECTED] = (int64_t)h[t * 3];
+      row[AV_CENSUS_LIVE_ACCEPTED] = (int64_t)h[t * 3 + 1];
+      row[AV_CENSUS_ABSENT_ACCEPTED] = (int64_t)h[t * 3 + 2];
+      // every counted node has exactly one class for the target
+      row[AV_CENSUS_ABSENT_REJECTED] = counted - row[0] - row[1] - row[3];
+    }
+  }
+  if (out->target_count_sum)
+    for (size_t t = 0; t < tn; ++t) out->target_count_sum[t] = (int64_t)h[tn * 3 + t];
+  if (out->count_hist)
+    for (size_t i = 0; i < 256; ++i) out->count_hist[i] = (int64_t)h[tn * 4 + i];
+  return AV_OK;
+}
+
 int av_discard_updates(av_engine* e) {
   AV_ENTER(e);
   return clear_log(e);
@@ -2746,6 +2810,9 @@ int av_set_option(av_engine* e, const char* name, int64_t value) {
   } else if (n == "materialize_run") {  // A/B: tiles per wave of the deferred state's write-back
     AV_CHECK(value >= 1 && value <= 64, AV_ERR_INVALID_ARG, "materialize_run must be 1..64");
     e->mat_run = (uint32_t)value;
+  } else if (n == "census_blocks") {  // workgroups of av_census's grid (0 = the engine's choice)
+    AV_CHECK(value >= 0 && value <= 65536, AV_ERR_INVALID_ARG, "census_blocks must be in [0, 65536]");
+    e->census_blocks = (uint32_t)value;
   } else if (n == "push_store") {  // A/B: 1 = plain stores (default), 0 = system scope, 2 = none (results invalid)
     AV_CHECK(value >= 0 && value <= 2, AV_ERR_INVALID_ARG, "push_store must be 0, 1 or 2");
     e->push_store = (uint32_t)value;

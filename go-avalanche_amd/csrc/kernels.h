@@ -501,6 +501,34 @@ hipError_t launch_gen_replay(uint64_t seed, uint32_t n0, uint32_t NL, uint32_t B
                              hipStream_t s);
 hipError_t launch_count_live(const uint32_t* planes, const uint32_t* valid, const uint32_t* byz, uint32_t n0,
                              uint32_t BL, uint32_t L, int honest_only, unsigned long long* out, hipStream_t s);
+// Network census (census.hip): class, count-sum, per-node and count-histogram tallies of local nodes
+// [nl0, nl1) in one pass over the A and K planes, read through the deferred count forms (kpend:
+// the engine's array when some tile may hold pending steps or kHiVirt, else nullptr) without
+// writing them back. Outputs (device, zeroed by the caller; nullptr = not wanted, its work is
+// skipped): tcls [tn][3] = nodes per target with a live rejected, live accepted, absent accepted
+// record, and *counted = the nodes counted (absent rejected = counted - the three); tsum [tn] = sum
+// of the live records' counts; ncls [nl1 - nl0][4] (16-byte aligned) = a node's targets per class
+// (AV_CENSUS_*); hist [2][128] = live records by accepted bit and count. blocks: workgroups (0 =
+// the device's resident set). The launcher fills the fields below the line.
+struct CensusParams {
+  const uint32_t* planes;
+  const uint32_t* kpend;
+  const uint32_t* valid;
+  const uint32_t* byz;
+  unsigned long long* tcls;
+  unsigned long long* tsum;
+  unsigned long long* hist;
+  unsigned long long* counted;
+  int32_t* ncls;
+  uint32_t BL, tn, n0;     // blocks per node, local targets, first local node (global id)
+  uint32_t honest_only;
+  // ---
+  uint32_t nl0, glo, ghi;  // first node; lane range
+  uint32_t tlo, nT;        // first tile, tiles
+  uint32_t P, C, S;        // tile classes (a lane's block is fixed within tile % P), chunks per class, tiles of a class per chunk
+  uint32_t bl_div64;       // BL divides 64: a node's lanes sit in one wave
+};
+hipError_t launch_census(CensusParams p, uint32_t nl0, uint32_t nl1, uint32_t blocks, hipStream_t s);
 // Batched poll sets (GetInvsForNextPoll of nodes [nl0, nl0 + n)): the per-node counts, their device
 // scan into offsets (n + 1, u64) and the CSR targets in one stream-ordered sequence; entries at or past
 // cap are not written. offs_out / targets_out may be host-mapped pinned memory (hipHostGetDevicePointer):

@@ -23,6 +23,7 @@ LIB_PATH = os.environ.get("AVHIP_LIB") or os.path.join(_PKG_ROOT, "lib", "libavh
 HEADER_PATH = os.path.join(os.path.dirname(_PKG_ROOT), "include", "avhip.h")
 
 AV_OK = 0
+AV_ERR_INVALID_ARG = -1
 AV_ERR_NOT_FOUND = -4
 AV_ERR_OVERFLOW = -5
 AV_ERR_PEER = -8
@@ -70,6 +71,18 @@ class Config(C.Structure):
     ]
 
 
+class CensusOut(C.Structure):  # include/avhip.h av_census_out
+    _fields_ = [
+        ("target_classes", C.c_void_p),
+        ("target_count_sum", C.c_void_p),
+        ("node_classes", C.c_void_p),
+        ("count_hist", C.c_void_p),
+    ]
+
+
+# av_census classes (include/avhip.h AV_CENSUS_*)
+CENSUS_LIVE_REJECTED, CENSUS_LIVE_ACCEPTED, CENSUS_ABSENT_REJECTED, CENSUS_ABSENT_ACCEPTED = 0, 1, 2, 3
+
 # every symbol declared in include/avhip.h (non-inline)
 PEER_HANDLE_BYTES = 320  # include/avhip.h AV_PEER_HANDLE_BYTES
 
@@ -78,7 +91,7 @@ EXPORTED = [
     "av_init_records", "av_add_targets", "av_set_valid", "av_register_votes", "av_is_accepted",
     "av_get_confidence", "av_get_invs", "av_get_invs_batch", "av_run_rounds", "av_replay_round_errs", "av_replay_prepare",
     "av_replay_rounds", "av_synchronize", "av_round_index", "av_updates_count", "av_fetch_updates",
-    "av_update_log_overflowed", "av_applied_votes", "av_alg_bytes", "av_alg_bytes_reread", "av_finalized_count", "av_live_records", "av_discard_updates", "av_read_records", "av_write_records", "av_read_pref", "av_sample_peers",
+    "av_update_log_overflowed", "av_applied_votes", "av_alg_bytes", "av_alg_bytes_reread", "av_finalized_count", "av_live_records", "av_census", "av_discard_updates", "av_read_records", "av_write_records", "av_read_pref", "av_sample_peers",
     "av_set_option", "av_set_timing", "av_kernel_stats", "av_layout_info", "av_comm_unique_id", "av_comm_init",
     "av_peer_handles", "av_peer_init", "av_get_round", "av_set_round", "av_log_base_round", "av_updates_digest",
     "av_updates_digest_range", "av_read_pref_words", "av_set_polling",
@@ -131,6 +144,7 @@ def lib():
         "av_materialize": (i32, [_vp]),
         "av_finalized_count": (i32, [_vp, P(i64)]),
         "av_live_records": (i32, [_vp, i32, P(i64)]),
+        "av_census": (i32, [_vp, i64, i64, i32, P(CensusOut)]),
         "av_discard_updates": (i32, [_vp]),
         "av_read_records": (i32, [_vp, i64, i64, i64, i64, _vp]),
         "av_write_records": (i32, [_vp, i64, i64, i64, i64, _vp]),
@@ -518,6 +532,29 @@ class Engine:
         out = C.c_int64(0)
         _check(lib().av_live_records(self._h, int(honest_only), C.byref(out)))
         return out.value
+
+    def census(self, n0=None, n1=None, honest_only=False, targets=True, count_sum=True, nodes=True, hist=True):
+        """Device-side census of local nodes [n0, n1) over this engine's targets (av_census): a dict
+        with, for each output asked for, "target_classes" int64 [targets][4] (nodes per CENSUS_*
+        class), "target_count_sum" int64 [targets] (sum of confidence >> 1 over live records),
+        "node_classes" int32 [n1 - n0][4] (a node's targets per class) and "count_hist" int64
+        [2][128] (live records by accepted bit and count). Reads through the deferred state."""
+        n0 = self.node_range[0] if n0 is None else n0
+        n1 = self.node_range[1] if n1 is None else n1
+        tn = self.target_range[1] - self.target_range[0]
+        res = {}
+        if targets:
+            res["target_classes"] = np.zeros((tn, 4), np.int64)
+        if count_sum:
+            res["target_count_sum"] = np.zeros(tn, np.int64)
+        if nodes:
+            res["node_classes"] = np.zeros((max(0, n1 - n0), 4), np.int32)
+        if hist:
+            res["count_hist"] = np.zeros((2, 128), np.int64)
+        out = CensusOut(*[res[k].ctypes.data if k in res else None
+                          for k in ("target_classes", "target_count_sum", "node_classes", "count_hist")])
+        _check(lib().av_census(self._h, n0, n1, int(honest_only), C.byref(out)))
+        return res
 
     def log_overflowed(self) -> bool:
         v = C.c_int32()

@@ -286,6 +286,35 @@ int av_applied_votes(av_engine* e, int64_t* out);
 int av_finalized_count(av_engine* e, int64_t* out);
 /* Live valid records now (honest_only: skip Byzantine nodes). */
 int av_live_records(av_engine* e, int32_t honest_only, int64_t* out);
+/* Network census: what IsAccepted / GetConfidence over every Processor
+ * (processor.go:125-140) and the example's stop test (main.go:143-162) would
+ * report, tallied on the device in one pass over the accepted and count planes
+ * with no nodes x targets intermediate. Counts local nodes [n0,n1) (global ids;
+ * honest_only: Byzantine nodes are skipped everywhere, their node_classes rows
+ * stay zero) over this engine's targets. In terms of the canonical record word
+ * w of av_read_records: absent = (w >> 17) >= 128, a = (w >> 16) & 1, class =
+ * 2 * absent + a, and count = (w >> 17) & 127 for live records; the census
+ * equals the one computed from av_read_records of the same range. Every counted
+ * node has exactly one class per local target: a target_classes row sums to the
+ * nodes counted, a counted node's node_classes row to the local target count.
+ * Validity (av_set_valid) does not change a record's class. Output pointers
+ * that are NULL skip their work. Stream-ordered after the rounds enqueued,
+ * synchronous, leaves the engine's deferred state in place.
+ * Shards: counts add across node shards and concatenate across target shards.
+ * AV_ERR_INVALID_ARG: out NULL, all four pointers NULL, or [n0,n1) outside the
+ * shard; n0 == n1 gives zeros. */
+#define AV_CENSUS_LIVE_REJECTED   0  /* live record, IsAccepted() false */
+#define AV_CENSUS_LIVE_ACCEPTED   1  /* live record, IsAccepted() true  */
+#define AV_CENSUS_ABSENT_REJECTED 2  /* no record, decision 0 (finalized rejected, or never added) */
+#define AV_CENSUS_ABSENT_ACCEPTED 3  /* no record, decision 1 (finalized accepted) */
+#define AV_CENSUS_CLASSES 4
+typedef struct {
+  int64_t* target_classes;   /* [local targets][4]  nodes of [n0,n1) per class, or NULL */
+  int64_t* target_count_sum; /* [local targets]     sum of (confidence >> 1) over live records, or NULL */
+  int32_t* node_classes;     /* [n1 - n0][4]        this node's local targets per class, or NULL */
+  int64_t* count_hist;       /* [2][128]            live records by accepted bit, then count, or NULL */
+} av_census_out;
+int av_census(av_engine* e, int64_t n0, int64_t n1, int32_t honest_only, const av_census_out* out);
 /* Drop pending StatusUpdates without copying them (long convergence runs). */
 int av_discard_updates(av_engine* e);
 /* Log entries pending, per kind: out = {single updates, slot records (2-4

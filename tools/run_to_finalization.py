@@ -3,7 +3,13 @@
 (or a round limit), one GPU, and report rounds-to-finalization plus the
 per-round kernel throughput.
 
-    python tools/run_to_finalization.py --workload c3 [--max-rounds 512] [--json out.json]
+    python tools/run_to_finalization.py --workload c3 [--max-rounds 512] [--json out.json] [--census]
+
+--census adds, per round and from one Engine.census() call over the honest nodes: the targets on
+which no honest node holds a live record, the honest nodes that hold none at all (the example's
+"fully finalized" nodes, main.go:143-162), and the minimum over targets of the larger of the two
+accepted-side node counts (nodes holding the target accepted, nodes that finalized it accepted):
+how far the least advanced target's acceptance has got.
 """
 import argparse
 import json
@@ -15,6 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "go-avalanche_amd", "python"))
 sys.path.insert(0, ROOT)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402,F401
 
 import avhip  # noqa: E402
@@ -27,6 +34,7 @@ def main():
     ap.add_argument("--max-rounds", type=int, default=512)
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0xA7A1A9C4)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--census", action="store_true", help="per-round network census (see above)")
     args = ap.parse_args()
     n, m, k, init_mode, init_param, byz, replay, desc = WORKLOADS[args.workload]
     assert not replay
@@ -50,6 +58,16 @@ def main():
         live = e.live_records(honest_only=True)
         per_round.append({"round": r, "kernel_ms": ms, "applied": e.applied_votes() - a0,
                           "finalized": e.finalized_count() - f0, "emitted": emitted, "honest_live": live})
+        if args.census:
+            c = e.census(honest_only=True, count_sum=False, hist=False)
+            tc, nc = c["target_classes"], c["node_classes"]
+            counted = nc.sum(axis=1) > 0  # Byzantine rows are zero
+            larger = np.maximum(tc[:, avhip.CENSUS_LIVE_ACCEPTED], tc[:, avhip.CENSUS_ABSENT_ACCEPTED])
+            per_round[-1].update({
+                "targets_without_live": int(((tc[:, 0] + tc[:, 1]) == 0).sum()),
+                "honest_nodes_done": int((counted & ((nc[:, 0] + nc[:, 1]) == 0)).sum()),
+                "min_accepted_side_nodes": int(larger.min()),
+            })
         if live == 0:
             done_round = r
             break
