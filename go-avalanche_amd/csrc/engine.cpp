@@ -271,6 +271,7 @@ struct av_engine {
   uint32_t dense_min = 0;  // option "dense_min" (kernels.h dense records; default dense_min(k))
   uint32_t wave_dense = 0;  // option "wave_dense" (kernels.h RoundParams::wave_dense; A/B)
   uint32_t uni_votes = 1;   // option "uni_votes" (kernels.h RoundParams::uni_votes)
+  uint32_t quiet_tiles = 1; // option "quiet_tiles" (kernels.h RoundParams::quiet_tiles; 0: every settled tile is walked)
   int32_t pub_mode = 0;
   uint32_t* readd = nullptr;     // [L] pub_mode 2: re-add marks
   uint32_t* died_out = nullptr;  // [L] pub_mode 2: records deleted this round
@@ -434,6 +435,7 @@ avk::RoundParams round_params(const av_engine* e, const uint32_t* replay) {
   p.dense_min = e->dense_min;
   p.wave_dense = e->wave_dense;
   p.uni_votes = e->uni_votes;
+  p.quiet_tiles = e->quiet_tiles;
   return p;
 }
 
@@ -2794,6 +2796,8 @@ int av_set_option(av_engine* e, const char* name, int64_t value) {
     AV_HIP(hipStreamSynchronize(e->stream));
   } else if (n == "uni_votes") {
     e->uni_votes = value != 0 ? 1u : 0u;
+  } else if (n == "quiet_tiles") {  // A/B: quiescent settled tiles skip the A read and the republish
+    e->quiet_tiles = value != 0 ? 1u : 0u;
   } else if (n == "wave_dense") {  // A/B: the dense log must hold one record per lane with updates
     AV_CHECK(value >= 0 && value <= 64, AV_ERR_INVALID_ARG, "bad wave_dense");
     e->wave_dense = (uint32_t)value;

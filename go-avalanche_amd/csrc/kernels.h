@@ -244,6 +244,9 @@ struct RoundParams {
   uint32_t dense_min;  // a lane with >= dense_min updates logs one dense record (default dense_min(k))
   uint32_t uni_votes;  // k = 8 warm sweep, uniform input (uni_in): general-path tiles take the reference word
                        // as their 8 votes instead of gathering them (option "uni_votes"; round_sweep.hip load_tile)
+  uint32_t quiet_tiles;  // k = 8 warm sweep, single-engine build (option "quiet_tiles", default 1): a settled tile
+                         // with two deferred rounds behind it and uniform input snapshots takes its +8 step with
+                         // no A-plane read and no republished row (round_sweep.hip "Quiescent tiles")
   uint32_t wave_dense; // k = 8 sweep (A/B option "wave_dense"): a wave with >= wave_dense lanes holding updates
                        // logs every such lane as a dense record (one store branch, no slot-word network); 0 off
 };

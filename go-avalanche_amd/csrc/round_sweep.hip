@@ -962,36 +962,57 @@ constexpr uint32_t kUniRun = 16;  // longest run settled_run_uni takes (p.tpw <=
 struct UniPre {
   uint32_t Av[kUniRun];
   uint32_t vw, refp, rin;
+  uint32_t bz[4];  // per lane: node nlA + lane + 64 j is Byzantine (uni_early)
   unsigned long long byzm[4];
 };
 
+// The part that depends on no tile word and on no slot word (the validity word, the Byzantine words of
+// the run's nodes): requested with the run's tile words, before the uniform test's slot words are
+// waited for, so that a quiescent wave, which does little else, waits for two memory latencies (the
+// kernel arguments, then everything it reads) and not for three in a row.
+__device__ __forceinline__ void uni_early(const RoundParams& p, uint32_t lane, uint32_t nlA, UniPre& u) {
+  u.vw = at_byte(p.valid, (lane & (p.BL - 1u)) * 4u);
+  // lanes past the run's nodes read the network's last node's word and drop it (uni_prefetch)
+#pragma unroll
+  for (uint32_t j = 0; j < 4u; ++j)
+    u.bz[j] = is_byz(p.byz, min(p.n0 + nlA + lane + 64u * j, p.n_nodes - 1u)) ? 1u : 0u;
+}
+
+// `qt`: the kernel-uniform part of the quiescent test holds (below, "Quiescent tiles"); the result is
+// the run's quiescent tiles (bit i: tile t0 + i), whose A words are not requested (an offset past the
+// resource, as for the tiles past the run); a run that is quiescent throughout does not read the
+// reference words either. After uni_early.
 template <int POL>
-__device__ __forceinline__ void uni_prefetch(const RoundParams& p, uint32_t lane, uint32_t t0, uint32_t tile_end,
-                                             uint32_t nlA, uint32_t nn, UniPre& u) {
+__device__ __forceinline__ uint32_t uni_prefetch(const RoundParams& p, uint32_t lane, uint32_t t0, uint32_t tile_end,
+                                                 uint32_t nn, uint32_t meta, bool qt, UniPre& u) {
   const uint32_t ntiles = tile_end - t0;
   const uint32_t bo = (lane & (p.BL - 1u)) * 4u;
+  uint32_t quiet = 0u;
+  if (qt)  // (lanes past the run hold meta = 0)
+    quiet = (uint32_t)__ballot((meta & (kPendAllLive | (kVMask << 8))) == (kPendAllLive | (kVUniform << 8)) &&
+                               (meta & 0xFFu) >= 2u);
   const __amdgpu_buffer_rsrc_t ta =
       __builtin_amdgcn_make_buffer_rsrc(p.planes + (size_t)t0 * (kPlanes * 64u), 0, (int)(ntiles * kPlanes * 64u * 4u),
                                         kRsrcWord3);
   const uint32_t aoff = (1536u + lane) * 4u;
 #pragma unroll
   for (uint32_t i = 0; i < kUniRun; ++i)  // tiles past the run: offset past the resource (reads 0, no access)
-    u.Av[i] = __builtin_amdgcn_raw_buffer_load_b32(ta, i < ntiles ? aoff + i * (kPlanes * 64u * 4u) : 0x80000000u, 0,
-                                                   POL > 0 ? 2 : 0);
-  u.vw = at_byte(p.valid, bo);
-  u.refp = at_byte(p.pref_prev, p.ref_node * p.PS * 4u + bo);  // every vote word this round
-  u.rin = p.uni_out ? at_byte(p.pref_in, p.ref_node * p.PS * 4u + bo) : 0u;
+    u.Av[i] = __builtin_amdgcn_raw_buffer_load_b32(
+        ta, i < ntiles && !((quiet >> i) & 1u) ? aoff + i * (kPlanes * 64u * 4u) : 0x80000000u, 0, POL > 0 ? 2 : 0);
+  const bool walk = quiet != (uint32_t)((1ull << ntiles) - 1ull);  // wave-uniform: some tile is left to the walk
+  u.refp = walk ? at_byte(p.pref_prev, p.ref_node * p.PS * 4u + bo) : 0u;  // every vote word this round
+  u.rin = walk && p.uni_out ? at_byte(p.pref_in, p.ref_node * p.PS * 4u + bo) : 0u;
   // the run's Byzantine bits, node nlA + rel at bit rel & 63 of byzm[rel >> 6]: up to 256 nodes (runs of
   // 16 tiles at BL >= 4, the merged runs of uni_merge on target shards)
 #pragma unroll
-  for (uint32_t j = 0; j < 4u; ++j)
-    u.byzm[j] = __ballot(lane + 64u * j < nn && is_byz(p.byz, p.n0 + nlA + lane + 64u * j));
+  for (uint32_t j = 0; j < 4u; ++j) u.byzm[j] = __ballot(lane + 64u * j < nn && u.bz[j] != 0u);
+  return quiet;
 }
 
 template <int POL, bool CC>
 __device__ __forceinline__ uint32_t settled_run_uni(const RoundParams& p, uint32_t lane, uint32_t t0,
                                                     uint32_t tile_end, uint32_t meta, uint32_t nlA, uint32_t nn,
-                                                    const UniPre& u, SweepAcc& acc) {
+                                                    const UniPre& u, uint32_t quiet, SweepAcc& acc) {
   const uint32_t ntiles = tile_end - t0;
   const uint32_t b = lane & (p.BL - 1u);
   const uint32_t vw = u.vw, refp = u.refp, rin = u.rin;
@@ -999,11 +1020,26 @@ __device__ __forceinline__ uint32_t settled_run_uni(const RoundParams& p, uint32
   // needs every honest row equal to their flip-flop pattern: rare), so that every settled word here
   // is the tile's A plane, with no per-lane Byzantine-bit lookup per tile
   if ((u.byzm[0] | u.byzm[1] | u.byzm[2] | u.byzm[3]) != 0ull) return 0u;
+  if constexpr (!CC) {
+    if (quiet) {
+      // Quiescent tiles (above k_round_sweep): one more deferred +8 step (lane i: tile t0 + i) and the
+      // counters; no A word, no published word. 8 B per tile: its kpend word read and written. Every
+      // lane is active in every tile but the network's last, which may be partial.
+      const bool mine = lane < ntiles && ((quiet >> lane) & 1u);
+      if (mine) p.kpend[t0 + lane] = ((meta & 0xFFu) + 1u) | kPendAllLive | (meta & kHiVirt);
+      const uint32_t last = (p.Lpad >> 6) - 1u;  // < t0 + 32 where it is tested (ntiles <= kUniRun)
+      const bool cut = last < tile_end && ((quiet >> (last - t0)) & 1u) && last * 64u + lane >= p.L;
+      acc.applied += 8u * (uint32_t)__popc(vw) * ((uint32_t)__popc(quiet) - (cut ? 1u : 0u));
+      acc.lane_bytes += mine ? 8u : 0u;
+      if (quiet == (uint32_t)((1ull << ntiles) - 1ull)) return quiet;  // (before the walk over the tile words)
+    }
+  }
   uint32_t cand = 0u;
   for (uint32_t i = 0; i < ntiles; ++i) {
     const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)meta, (int)i);
     if ((m & (kPendAllLive | (kVMask << 8))) == (kPendAllLive | (kVUniform << 8))) cand |= 1u << i;
   }
+  cand &= ~quiet;
   uint32_t Av[kUniRun], Ov[kUniRun];
 #pragma unroll
   for (uint32_t i = 0; i < kUniRun; ++i) Av[i] = u.Av[i];
@@ -1053,7 +1089,7 @@ __device__ __forceinline__ uint32_t settled_run_uni(const RoundParams& p, uint32
     acc.applied += applied;
     acc.lane_bytes += bytes;
     if (p.uni_out) acc.umis |= umis;
-    return done;
+    return done | quiet;
   }
   uint32_t done = 0u, applied = 0u, bytes = 0u, umis = 0u;
 #pragma unroll
@@ -1093,6 +1129,57 @@ __device__ __forceinline__ uint32_t settled_run_uni(const RoundParams& p, uint32
   return done;
 }
 
+// Quiescent tiles (p.quiet_tiles, option "quiet_tiles", default 1; the single-engine build, CC ==
+// false; 0 restores the walk of every settled tile). A tile of a wave's run is quiescent in round r
+// when
+//  * it is a settled candidate as settled_run_uni tests it (kPendAllLive, kVUniform),
+//  * its incoming pend (kpend low byte) is >= 2: it deferred its count step in rounds r - 1 and r - 2,
+//  * `uniform` and `prev_uni` hold: every row of pref_in is the reference row of pref_prev, and every
+//    row of pref_prev the reference row of the snapshot before it (whatever option uni_votes says),
+//  * its run holds no Byzantine node (settled_run_uni's own gate).
+// Then (1) the reference node's row of pref_prev is one of "every row" of it, so this round's vote
+// word w is last round's w'; (2) the tile deferred in r - 1, which process_tile, settled_run and
+// settled_run_uni grant only when every polled record agreed with all 8 votes and nothing flipped:
+// A & P0 == w' & P0 at the end of r - 1, and A has not changed since, so the settled test of round r
+// holds before A is loaded; (3) pref_out is the ring buffer that held the snapshot of round r - 2's
+// input: every row of it is the row's A plane at the start of r - 2 (published by round r - 3, or by
+// the call that rewrote the records since), and a tile that deferred in r - 2 and r - 1 still has
+// that A: the store would rewrite the word already there (the fact `known` in process_tile and the
+// need-masked peer pushes are built on). More: the tile's own row of pref_in, published in r - 1, is
+// its A and is a uniform row, so A equals the reference word of pref_in on the whole word: no
+// mismatch to tag (umis). A quiescent tile's one effect is pend + 1 and the applied / byte counters
+// (8 B: its kpend word read and written); rows, V, A, K, the log and the uniform tag stay.
+// Threshold: pend >= 2, the least for (3); (2) alone needs pend >= 1.
+//
+// Reference-row flags (REF): the settled tiles of a uniform round write none already
+// (settled_run_uni does not), and a flag byte carries its snapshot's tag (ref_tag), so the byte a
+// quiescent tile leaves in pref_out's flags is three rounds old and reads as "unflagged": gather.
+//
+// Everything else that writes kpend, a record plane, the validity words or a snapshot row, and why
+// no tile is taken as quiescent afterwards while its row of pref_out or its A differs from what
+// the walk would publish. Two guards: a write-back clears pend (k_materialize, launched by
+// materialize_votes / materialize_counts in engine.cpp, zeroes every kpend word), so two deferred
+// rounds must follow it; ref_invalidate drops uni_ok of all three buffers, so `uniform` is false in
+// the next round and prev_uni in the next two.
+//  * av_register_votes(_batch), av_add_targets, av_write_records: materialize_votes first (pend = 0,
+//    kPendAllLive gone) and ref_invalidate; they republish the rows they change into the current
+//    snapshot (k_register_votes, k_add_targets, refresh_pref), which is pref_out three rounds later:
+//    (3) holds with "the call that rewrote the records".
+//  * av_set_valid: materialize_votes (pend = 0) and ref_invalidate; A and the rows are untouched, and
+//    the new polled set is first seen by the general path (kPendAllLive cleared).
+//  * av_init_records: kpend zeroed, ref_invalidate, every plane and the current snapshot rewritten;
+//    the fresh round after it defers nothing (klazy needs a warm round).
+//  * av_materialize and every other write-back: pend = 0. av_read_records, av_census, av_read_pref
+//    read through the deferred forms and write nothing.
+//  * av_set_option (every option, this one too): ref_invalidate; count_lazy and k_hi_virtual write
+//    back first; responder republishes and leaves the sweep.
+//  * the replay, capped and first-generation round kernels, and a sweep round that is not klazy:
+//    launch_one_round / launch_replay_fused write the counts back first (pend = 0) and leave
+//    uni_ok of the buffer they write false (replay, capped: uni is false) or run the kconsume round,
+//    which clears kpend itself.
+//  * peer pushes, the barrier's slot copy and RCCL gathers write snapshot buffers of node-sharded
+//    engines only: those run the CC build, which has no quiescent path.
+//
 // MODE: kModeWarm (sim, every consider plane all-ones), kModeCheck (sim, per
 // tile: the oldest consider plane decides), kModeReplay (replayed votes),
 // kModeAblate (kModeCheck with the peer gather replaced by a coalesced read of
@@ -1130,9 +1217,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == kMo
   if (uniform)
     for (uint32_t r = 0; r < p.uni_world; ++r) uniform = uniform && p.uni_in[r] != p.round;
   // (and of pref_prev: its slots carry round - 1's tag if a row of it differed)
-  bool uniform_prev = uniform && p.uni_prev != nullptr && K == 8 && p.uni_votes && p.vv;
-  if (uniform_prev)
-    for (uint32_t r = 0; r < p.uni_world; ++r) uniform_prev = uniform_prev && p.uni_prev[r] != p.round - 1u;
+  // prev_uni: whatever the uni_votes option says (the quiescent tiles need it too)
+  bool prev_uni = uniform && p.uni_prev != nullptr && K == 8 && ((p.uni_votes && p.vv) || (!CC && p.quiet_tiles));
+  if (prev_uni)
+    for (uint32_t r = 0; r < p.uni_world; ++r) prev_uni = prev_uni && p.uni_prev[r] != p.round - 1u;
+  const bool uniform_prev = prev_uni && p.uni_votes && p.vv;
   const uint32_t uflags = (K == 8 && uniform && p.uni_votes && p.vv ? kUniVotes : 0u) | (uniform_prev ? kUniPrev : 0u);
   if constexpr (MODE == kModeWarmPipe) {
     // software-pipelined: tile t + nwaves's loads (state, peer draw, gathers)
@@ -1187,12 +1276,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == kMo
           const bool uni_ok = p.uni_in && p.lean && p.settled_fast && p.klazy && p.vv && nn <= 256u &&
                               tile_end - tile <= kUniRun;
 #if AVK_UNI_PREFETCH
-          if (uni_ok) uni_prefetch<POL>(p, lane, tile, tile_end, nlA, nn, upre);
+          if (uni_ok) {
+            uni_early(p, lane, nlA, upre);
+            (void)uni_prefetch<POL>(p, lane, tile, tile_end, nn, 0u, false, upre);
+          }
 #endif
           // the run's per-tile words, one lane per tile (tpw <= 16)
           const uint32_t ti = tile + lane;
           const uint32_t st = p.vv && ti < tile_end ? p.vstale[ti] : 0u;
           const uint32_t kw = (p.klazy || p.kconsume) && ti < tile_end ? p.kpend[ti] : 0u;
+#if !AVK_UNI_PREFETCH
+          if constexpr (!CC) {  // (the counting build requests them where it always did, below)
+            if (uni_ok) uni_early(p, lane, nlA, upre);
+          }
+#endif
           wd.meta = (st << 8) | (kw & (kPendAllLive | kHiVirt | 0xFFu));
           wd.t0 = tile;
           wd.nlA = nlA;
@@ -1200,10 +1297,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == kMo
           // uniform rows: the run's settled candidates first, with no draw; the draw only if a tile is left
           const uint32_t all_tiles = (uint32_t)((1ull << (tile_end - tile)) - 1ull);
           if (uni_ok && uniform) {
+            // the run's quiescent tiles (above): settled candidates with two deferred rounds behind them,
+            // both input snapshots uniform (a Byzantine node in the run: settled_run_uni drops them)
+            const bool qt = !CC && prev_uni && p.quiet_tiles;
 #if !AVK_UNI_PREFETCH
-            uni_prefetch<POL>(p, lane, tile, tile_end, nlA, nn, upre);
+            if constexpr (CC) uni_early(p, lane, nlA, upre);
+            const uint32_t quiet = uni_prefetch<POL>(p, lane, tile, tile_end, nn, wd.meta, qt, upre);
+#else
+            const uint32_t quiet = 0u;
+            (void)qt;
 #endif
-            uni_done = settled_run_uni<POL, CC>(p, lane, tile, tile_end, wd.meta, nlA, nn, upre, acc);
+            uni_done = settled_run_uni<POL, CC>(p, lane, tile, tile_end, wd.meta, nlA, nn, upre, quiet, acc);
             uni_ran = true;
           }
           const bool any_stale = __ballot((st & kVMask) == kVStale) != 0ull;

@@ -411,6 +411,9 @@ int av_sample_peers(av_engine* e, int64_t round, int64_t n0, int64_t n1, int32_t
  * wave's pushes queued in LDS and issued after its tiles), "peer_fine" (1),
  * "uni_votes" (1: in a round whose input snapshot is uniform, every tile takes
  * the reference word as its votes instead of gathering them; exact),
+ * "quiet_tiles" (1: a settled tile with two deferred rounds behind it and two
+ * uniform input snapshots takes its count step with no A-plane read and no
+ * republished row; engines without an exchange; exact),
  * "wave_dense" (0; n: a wave with >= n lanes holding updates logs them all as
  * dense records; exact, measured slower).
  * StatusUpdate delivery: "enc_buckets" (2^26: (round, node) buckets per
