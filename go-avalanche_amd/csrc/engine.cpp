@@ -19,6 +19,7 @@
 
 #include "../../include/avhip.h"
 #include "kernels.h"
+#include "round_plan.h"
 
 namespace {
 
@@ -39,6 +40,13 @@ int fail(int code, const char* fmt, ...) {
     hipError_t _e = (call);                                                                             \
     if (_e != hipSuccess) return fail(AV_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_e), \
                                       __FILE__, __LINE__);                                              \
+  } while (0)
+
+// propagate an AV_ERR_* code
+#define AV_TRY(call)              \
+  do {                            \
+    int _rc = (call);             \
+    if (_rc != AV_OK) return _rc; \
   } while (0)
 
 #define AV_CHECK(cond, code, ...) \
@@ -79,23 +87,21 @@ struct av_engine {
   // words per node row of the preference tables: BL rounded up to a power of two (BL <= 32) or to a
   // multiple of 32 (BL > 32), so that a gathered row covers whole 128-B lines (avk::pref_stride)
   uint32_t PS = 0;
+  // what the host knows about the records, and the one place each fact changes (round_plan.h)
+  avk::RecordFacts facts;
   // reference rows (kernels.h ref_node / rflag_*): one flag byte per node after the preference words
-  // of every snapshot buffer (so rotation, IPC export and peer pushes carry them); rflag_ok[b]: the
-  // flags of buffer b were written by the round that wrote its rows, against ref_node's row of the
-  // buffer that round read, and nothing has written either buffer since
+  // of every snapshot buffer (so rotation, IPC export and peer pushes carry them; facts.rflag_ok)
   // option "ref_rows" (default off: measured slower): the flag loads, the reference
   // word and the writer's ballot + byte store cost more issue/latency than the 8 gathers they replace
   bool ref_rows = false;
   int64_t ref_node = -1;  // first honest node (chosen at the first round that can use it); -2: none
   size_t rflag_off = 0;   // byte offset of the flags in a snapshot buffer
-  bool rflag_ok[3] = {false, false, false};
   // option "uniform_rows" (default on; kernels.h uni_*): every snapshot buffer carries one mismatch
-  // slot per rank at word uni_off; uni_ok[b]: buffer b was written by a sweep round that tagged them
+  // slot per rank at word uni_off (facts.uni_ok)
   bool uni_rows = true;
   uint32_t uni_merge = 1;  // option "uni_merge": runs per wave in a round with a uniform input (kernels.h)
   bool k_hi_virtual = true;  // option "k_hi_virtual": the K4..K7 group left unstored while counts are < 16 (kernels.h kHiVirt)
   size_t uni_off = 0;
-  bool uni_ok[3] = {false, false, false};
 
   int cur = 0;
   static int nxt(int c) { return c == 2 ? 0 : c + 1; }
@@ -106,9 +112,7 @@ struct av_engine {
   uint32_t* vstale = nullptr;  // [tiles]
   // deferred count planes (kernels.h klazy): option "count_lazy"
   uint32_t* kpend = nullptr;   // [tiles]
-  bool k_pend = false;         // some tile may hold pending steps or flags
   bool count_lazy = true;
-  bool v_stale = false;        // some tile may be stale
   bool virtual_votes = true;
   uint32_t vv_min_bl = 16;
   uint32_t* valid = nullptr;
@@ -138,10 +142,6 @@ struct av_engine {
   // field's width, max(24, bits of N); the log spans at most 2^(64 - round_shift) rounds
   uint32_t round_shift = 52;
   int64_t max_log_rounds() const { return (int64_t)1 << (64 - round_shift); }
-  // every consider bit ever shifted in was 1 (no replay, no neutral drop-in
-  // vote, no write_records): an all-ones oldest consider plane implies all
-  // consider planes are all-ones (lets k_round_fast skip them)
-  bool c_monotone = true;
   bool plane_nt = true;  // tuning option "plane_nt" (A/B on MI355X: -8 % kernel time warm, -16 % cold)
   bool ablate_gather = false;  // diagnostics option "ablate_gather" (invalid results)
   uint32_t ablate_node = 0;  // diagnostics option "ablate_node" (k_round_node, invalid results)
@@ -175,19 +175,8 @@ struct av_engine {
   // >= 15000 waves (C4: 500k tiles, 16 per wave; C3's 98k tiles: 4 — 8 per wave leaves two generations
   // of waves and was 6 % slower)
   uint32_t tiles_per_wave = 0;
-  // every consider plane of every lane is all-ones: set after a sim round with k >= 8 in which every
-  // live record was polled (all targets valid, uncapped); cleared by anything that can write a 0
-  // consider bit (init, add, write_records, drop-in votes, replay)
-  bool warm_all = false;
-  // every record is a NewVoteRecord from av_init_records (votes = consider =
-  // count = 0): the next sweep round reads only the A plane (kernels.h fresh)
-  bool fresh = false;
   uint32_t bl_magic = 1, bl_sh1 = 0, bl_sh2 = 0;
   uint32_t store_policy = 0;  // option "store_policy": 2 = sc1 (write-through) plane stores, 3 = nt sc1
-  // upper bound on any live record's count (confidence >> 1) at the start of the next round: a
-  // round adds at most k, init/add start at 0, anything else sets it to 127. While it is < 120 no
-  // record can finalize in the next round (k <= 8), so the capped path skips its exact pass.
-  int count_bound = 127;
   std::vector<uint32_t> valid_host;
   // replay stream
   uint32_t* replay = nullptr;
@@ -331,11 +320,7 @@ int set_device(av_engine* e) {
   return AV_OK;
 }
 
-#define AV_ENTER(e)              \
-  do {                           \
-    int _rc = set_device(e);     \
-    if (_rc != AV_OK) return _rc; \
-  } while (0)
+#define AV_ENTER(e) AV_TRY(set_device(e))
 
 bool local_node(const av_engine* e, int64_t node) { return node >= e->n0 && node < e->n1; }
 bool local_target(const av_engine* e, int64_t t) { return t >= e->t0 && t < e->t1; }
@@ -357,14 +342,6 @@ struct Scratch {
     return e;
   }
 };
-
-// Anything but a reference-row sweep round that writes a snapshot buffer
-// (drop-in votes, adds, writes, init, validity/publish-rule refreshes, peer
-// and RCCL set-up, other round kernels) leaves its flags stale.
-void ref_invalidate(av_engine* e) {
-  e->rflag_ok[0] = e->rflag_ok[1] = e->rflag_ok[2] = false;
-  e->uni_ok[0] = e->uni_ok[1] = e->uni_ok[2] = false;
-}
 
 avk::RoundParams round_params(const av_engine* e, const uint32_t* replay) {
   avk::RoundParams p{};
@@ -389,7 +366,7 @@ avk::RoundParams round_params(const av_engine* e, const uint32_t* replay) {
   p.applied = e->applied;
   p.bytes = e->bytes;
   p.finalized = e->finalized;
-  p.warm_skip = e->c_monotone ? 1u : 0u;
+  p.warm_skip = e->facts.c_monotone ? 1u : 0u;
   p.plane_nt = e->plane_nt ? 1u : 0u;
   p.ablate_gather = e->ablate_gather ? 1u : 0u;
   p.ablate_emit = (uint32_t)e->ablate_emit;
@@ -412,16 +389,12 @@ avk::RoundParams round_params(const av_engine* e, const uint32_t* replay) {
   p.round_rel = (uint32_t)(e->round - e->log_base);
   p.round_shift = e->round_shift;
   p.peer_mode = e->cfg.peer_mode;
-  p.warm_all = e->warm_all ? 1u : 0u;
+  p.warm_all = e->facts.warm_all ? 1u : 0u;
   p.store_policy = e->store_policy;
-  p.node_flags = nullptr;
   p.bl_magic = e->bl_magic;
   p.bl_sh1 = e->bl_sh1;
   p.bl_sh2 = e->bl_sh2;
   p.kpend = e->kpend;
-  p.klazy = 0u;
-  p.kconsume = 0u;
-  p.fresh = 0u;
   p.tn = (uint32_t)(e->t1 - e->t0);
   p.nopipe = e->sweep_nopipe ? 1u : 0u;
   p.tpw = e->wave_runs && e->sweep_blocks ? 1u : 0u;
@@ -439,34 +412,20 @@ avk::RoundParams round_params(const av_engine* e, const uint32_t* replay) {
   return p;
 }
 
-// Write back the vote planes of tiles the last warm k = 8 sim round left
-// stale (kernels.h vv); every path that reads or writes records other than
-// such a round calls this first.
-int materialize_votes_only(av_engine* e) {
-  if (!e->v_stale) return AV_OK;
-  AV_HIP(avk::launch_materialize(round_params(e, nullptr), true, false, e->stream));
-  e->v_stale = false;
+// Write back deferred state, one k_materialize pass. votes: the vote planes of tiles the last warm
+// k = 8 sim round left stale (kernels.h vv); every path that reads or writes records other than such
+// a round asks for them first. counts: the pending +8 steps of deferred count planes (kernels.h
+// klazy); every path that reads or writes counts other than a klazy round asks for them first.
+int materialize(av_engine* e, bool votes, bool counts) {
+  votes = votes && e->facts.v_stale;
+  counts = counts && e->facts.k_pend;
+  if (!votes && !counts) return AV_OK;
+  AV_HIP(avk::launch_materialize(round_params(e, nullptr), votes, counts, e->stream));
+  if (votes) e->facts.votes_written_back();
+  if (counts) e->facts.counts_written_back();
   return AV_OK;
 }
-
-// Apply the pending +8 steps of deferred count planes (kernels.h klazy);
-// every path that reads or writes counts other than a klazy round calls this
-// first.
-int materialize_counts(av_engine* e) {
-  if (!e->k_pend) return AV_OK;
-  AV_HIP(avk::launch_materialize(round_params(e, nullptr), false, true, e->stream));
-  e->k_pend = false;
-  return AV_OK;
-}
-
-// Both deferred forms (vote planes, count planes) written back, in one pass.
-int materialize_votes(av_engine* e) {
-  if (!e->v_stale && !e->k_pend) return AV_OK;
-  AV_HIP(avk::launch_materialize(round_params(e, nullptr), e->v_stale, e->k_pend, e->stream));
-  e->v_stale = false;
-  e->k_pend = false;
-  return AV_OK;
-}
+int materialize_votes(av_engine* e) { return materialize(e, true, true); }
 
 // A serial peer group's members store into each other's buffers: once any member was destroyed (its
 // buffers freed), no member may push or exchange need masks any more.
@@ -479,10 +438,7 @@ int group_alive(const av_engine* e) {
 // Peer-push exchange: copy this rank's rows of snapshot buffer `b` into every
 // peer replica (a full resynchronisation of those rows).
 int push_own_rows(av_engine* e, int b) {
-  {
-    int rc = group_alive(e);
-    if (rc != AV_OK) return rc;
-  }
+  AV_TRY(group_alive(e));
   avk::PeerPtrs dst{};
   uint32_t n = 0;
   for (int r = 0; r < e->peer_world; ++r)
@@ -540,8 +496,7 @@ int mask_setup(av_engine* e) {
   if (!e->tiles_per_wave && !e->sweep_blocks_explicit && e->BL >= 16 && e->peer_world >= 4) {
     e->tiles_per_wave = 16;
     e->sweep_blocks = default_sweep_blocks(e, false);
-    int rc = relayout_log_if_empty(e);  // fewer writer waves
-    if (rc != AV_OK) return rc;
+    AV_TRY(relayout_log_if_empty(e));  // fewer writer waves
   }
   e->masked = e->peer_mask && e->peer_world >= 2 && e->peer_world <= 9 && mask_layout_ok(e) && e->needin;
   if (!e->masked) return AV_OK;
@@ -577,15 +532,11 @@ int need_draw(av_engine* e, int64_t w, hipStream_t s) {
 
 int need_gen(av_engine* e, int64_t w) {
   if (!e->masked || e->need_pushed == w) return AV_OK;
-  {
-    int rc = group_alive(e);
-    if (rc != AV_OK) return rc;
-  }
+  AV_TRY(group_alive(e));
   if (e->need_drawn_w == w) {
     AV_HIP(hipStreamWaitEvent(e->stream, e->need_drawn, 0));  // drawn ahead on the side stream
   } else {
-    int rc = need_draw(e, w, e->stream);
-    if (rc != AV_OK) return rc;
+    AV_TRY(need_draw(e, w, e->stream));
   }
   AV_HIP(avk::launch_need_push(e->need_mine, (uint32_t)e->N, e->NL, avk::kNeedWin, (uint32_t)e->peer_world,
                                (uint32_t)e->peer_rank, (uint32_t)(w & 1), e->peer_needin, e->stream));
@@ -602,8 +553,7 @@ int need_gen(av_engine* e, int64_t w) {
 int need_draw_ahead(av_engine* e, int64_t w) {
   if (!e->masked || e->group || e->need_drawn_w == w || e->need_pushed >= w) return AV_OK;
   AV_HIP(hipStreamWaitEvent(e->need_stream, e->need_free, 0));
-  int rc = need_draw(e, w, e->need_stream);
-  if (rc != AV_OK) return rc;
+  AV_TRY(need_draw(e, w, e->need_stream));
   AV_HIP(hipEventRecord(e->need_drawn, e->need_stream));
   e->need_drawn_w = w;
   return AV_OK;
@@ -614,8 +564,7 @@ int ref_pick(av_engine* e);
 // After the barrier that ordered every rank's need_gen of window w: the per-row peer masks.
 int need_combine(av_engine* e, int64_t w) {
   if (!e->masked || e->need_ready == w || e->need_pushed != w) return AV_OK;
-  int rc = ref_pick(e);  // the reference row (uniform rows) is read by every rank
-  if (rc != AV_OK) return rc;
+  AV_TRY(ref_pick(e));  // the reference row (uniform rows) is read by every rank
   const uint32_t ref_local =
       e->ref_node >= e->n0 && e->ref_node < e->n1 ? (uint32_t)(e->ref_node - e->n0) : 0xFFFFFFFFu;
   AV_HIP(avk::launch_need_combine(e->needin, (uint32_t)e->peer_world, (uint32_t)e->peer_rank, (uint32_t)(w & 1),
@@ -643,19 +592,14 @@ int peer_failed(av_engine* e) {
   return AV_OK;
 }
 
-#define AV_PEER_CHECK(e)          \
-  do {                            \
-    int _rc = peer_failed(e);     \
-    if (_rc != AV_OK) return _rc; \
-  } while (0)
+#define AV_PEER_CHECK(e) AV_TRY(peer_failed(e))
 
 // For calls that return results: every round enqueued so far (and its
 // barrier) completes first, then the flag decides.
 #define AV_PEER_SYNC_CHECK(e)                                      \
   do {                                                             \
     if ((e)->peer_world > 1) AV_HIP(hipStreamSynchronize((e)->stream)); \
-    int _rc = peer_failed(e);                                      \
-    if (_rc != AV_OK) return _rc;                                  \
+    AV_TRY(peer_failed(e));                                        \
   } while (0)
 
 // Growable device scratch owned by the engine.
@@ -690,13 +634,21 @@ int ref_pick(av_engine* e) {
   return AV_OK;
 }
 
-int launch_one_round(av_engine* e, const uint32_t* replay) {
-  AV_CHECK(e->round - e->log_base < e->max_log_rounds(), AV_ERR_OVERFLOW,
+avk::RoundPlan plan_for(const av_engine* e, bool replay) {
+  const avk::PlanShape shape{e->k,       e->BL,         e->N,           e->NL,       e->PS,
+                             e->capped,  e->peer_world, e->comm != nullptr, e->pub_mode, e->any_nopoll};
+  const avk::PlanKnobs knobs{e->kernel,       e->virtual_votes, e->vv_min_bl, e->count_lazy,    e->k_hi_virtual,
+                             e->ref_rows,     e->uni_rows,      e->ablate_gather, e->unsynced_shard};
+  return avk::plan_round(e->facts, shape, knobs, replay);
+}
+
+int round_checks(const av_engine* e, int64_t rounds) {
+  AV_CHECK(e->round + rounds - 1 - e->log_base < e->max_log_rounds(), AV_ERR_OVERFLOW,
            "StatusUpdate log spans %lld rounds: call av_fetch_updates more often", (long long)e->max_log_rounds());
   if (e->group) {
     // serial group: round r of rank i is enqueued after round r of every lower rank and before
     // round r of every higher one (the stream order is the exchange's barrier)
-    for (const av_engine* m : e->group->members) AV_CHECK(m, AV_ERR_UNSUPPORTED, "peer group: a rank was destroyed");
+    AV_TRY(group_alive(e));
     for (const av_engine* m : e->group->members)
       if (m != e)
         AV_CHECK(m->round == e->round + (m->peer_rank < e->peer_rank ? 1 : 0), AV_ERR_UNSUPPORTED,
@@ -707,59 +659,24 @@ int launch_one_round(av_engine* e, const uint32_t* replay) {
                e->unsynced_shard,
            AV_ERR_UNSUPPORTED,
            "node-sharded engine needs av_comm_init before running rounds");
-  avk::RoundParams p = round_params(e, replay);
-  // responder variants and non-polling nodes run the first-generation kernels
-  const bool compat = e->pub_mode != 0 || e->any_nopoll;
-  AV_CHECK(!(compat && e->capped && (e->pub_mode == 2 || e->any_nopoll)), AV_ERR_UNSUPPORTED,
-           "the example responder and av_set_polling need M <= 4096 (uncapped)");
-  // the sweep addresses the preference table by 32-bit byte offsets
-  const bool sweep = e->kernel == 2 && e->k <= 8 && !e->capped && !compat && (uint64_t)e->N * e->PS < (1ull << 30);
-  // the round after av_init_records: planes known to be zero are not read
-  const bool fresh = e->fresh && sweep && !replay && !e->ablate_gather;
-  // the sweep's warm sim modes (launch_sweep_k): every consider plane all-ones
-  const bool warm = sweep && !replay && e->c_monotone && e->warm_all && !e->ablate_gather && !fresh;
-  // vote planes may be left unstored: warm (or fresh) k = 8 sim rounds
-  // below vv_min_bl only the uniform form (a settled tile's V = A: nothing to regather)
-  const bool vv = e->virtual_votes && e->k == 8 && (warm || fresh);
-  const bool vv_uniform = vv && e->BL < e->vv_min_bl;
-  if (!vv) {
-    int rc = materialize_votes_only(e);
-    if (rc != AV_OK) return rc;
-  }
-  p.vv = vv ? 1u : 0u;
-  p.vv_uniform = vv_uniform ? 1u : 0u;
-  if (vv) e->v_stale = true;
-  p.fresh = fresh ? 1u : 0u;
-  // count planes may be deferred: warm k = 8 sim rounds while no record can
-  // finalize (every true count < 120 at round start); the first warm round
-  // that can finalize applies the pending steps itself (kconsume)
-  const bool klazy = e->count_lazy && warm && e->k == 8 && e->count_bound < 120;
-  const bool kconsume = !klazy && e->k_pend && warm && e->k == 8;
-  if (!klazy && !kconsume) {
-    int rc = materialize_counts(e);
-    if (rc != AV_OK) return rc;
-  }
-  p.klazy = klazy ? 1u : 0u;
-  p.kconsume = kconsume ? 1u : 0u;
-  p.hivirt = e->k_hi_virtual && e->k == 8 ? 1u : 0u;
-  if (klazy) e->k_pend = true;
-  if (kconsume) e->k_pend = false;
-  bool all_valid = true;
-  for (uint32_t b = 0; b < e->BL; ++b) {
-    const int64_t tb = e->t0 + 32ll * b;
-    const int64_t r = std::min<int64_t>(e->t1 - tb, 32);
-    all_valid &= e->valid_host[b] == (r >= 32 ? ~0u : ((1u << r) - 1u));
-  }
-  // peer-push exchange: the sweep kernel's sim rounds push changed words; any
-  // other round is followed by a full push of this rank's rows (uniform across
-  // ranks: it depends only on the engine configuration and the call)
-  const bool peer = e->peer_world > 1;
-  const int nb = av_engine::nxt(e->cur);
-  if (peer && sweep && !replay) {
+  return AV_OK;
+}
+
+bool all_targets_valid(const av_engine* e) {
+  for (uint32_t b = 0; b < e->BL; ++b)
+    if (e->valid_host[b] != avk::real_mask((uint32_t)(e->t1 - e->t0), b)) return false;
+  return true;
+}
+
+// peer-push exchange: the sweep kernel's sim rounds push changed words into buffer nb's replicas; any
+// other round is followed by a full push of this rank's rows (uniform across
+// ranks: it depends only on the engine configuration and the call)
+void fill_push_params(const av_engine* e, bool sweep_sim, int nb, avk::RoundParams& p) {
+  if (e->peer_world > 1 && sweep_sim) {
     p.push_n = (uint32_t)e->peer_world - 1u;
     p.push_dst = e->push_tbl + (size_t)nb * avk::kMaxPeers;
     if (e->masked) {  // need-masked pushes: this round's row masks (window of push round e->round)
-      const int64_t w = e->round / avk::kNeedWin;  // combined below (need_combine) if not yet
+      const int64_t w = e->round / avk::kNeedWin;  // combined before the launch (need_combine) if not yet
       const bool have = e->need_ready == w || e->need_pushed == w;
       p.need = have ? e->needmask + (size_t)(e->round % avk::kNeedWin) * e->NL : nullptr;
       p.stale = e->stale + (size_t)nb * e->NL * e->segs;
@@ -769,125 +686,149 @@ int launch_one_round(av_engine* e, const uint32_t* replay) {
     p.push_defer = e->push_defer ? 1u : 0u;
     p.push_store = e->push_store;
   }
-  p.count_changed = (p.push_n || e->count_changed) && sweep && !replay ? 1u : 0u;
+  p.count_changed = (p.push_n || e->count_changed) && sweep_sim ? 1u : 0u;
   p.changed = e->changed;
-  // reference rows: sweep rounds at k = 8 with a node's lanes inside one wave
-  bool refr = e->ref_rows && sweep && e->k == 8 && !replay && 64 % e->BL == 0 && !e->comm && !e->ablate_gather;
-  if (refr) {
-    int rc = ref_pick(e);
-    if (rc != AV_OK) return rc;
-    refr = e->ref_node >= 0;
+}
+
+// Reference rows and uniform rows where the plan allows them and an honest reference node exists
+// (the plan's two flags are cleared where none does).
+int fill_row_params(av_engine* e, avk::RoundPlan& plan, int nb, avk::RoundParams& p) {
+  if (plan.ref_rows || plan.uni_rows) {
+    AV_TRY(ref_pick(e));
+    plan.ref_rows = plan.ref_rows && e->ref_node >= 0;
+    plan.uni_rows = plan.uni_rows && e->ref_node >= 0;
   }
-  if (refr && e->round - e->rflag_clear_round >= 120) {
+  if (plan.ref_rows && e->round - e->rflag_clear_round >= 120) {
     // flag bytes carry a 7-bit snapshot tag (round_sweep.hip ref_tag): every buffer's flags are
     // cleared before 128 rounds have passed since the last clear, whatever kind of round ran in
     // between (replay, capped, non-refr), so no byte outlives its tag's period
     for (int b = 0; b < 3; ++b)
       AV_HIP(hipMemsetAsync(reinterpret_cast<uint8_t*>(e->pref[b]) + e->rflag_off, 0, (size_t)e->N, e->stream));
     e->rflag_clear_round = e->round;
-    ref_invalidate(e);
+    e->facts.snapshot_written();
   }
-  if (refr) {
+  if (plan.ref_rows) {
     p.ref_node = (uint32_t)e->ref_node;
     p.ps_shift = (uint32_t)__builtin_ctz(e->PS * 4u);
     p.rflag_off = (uint32_t)e->rflag_off;
-
     p.rflag_out = reinterpret_cast<uint8_t*>(e->pref[nb]) + e->rflag_off;
-    p.rflag_in = e->rflag_ok[e->cur] ? reinterpret_cast<const uint8_t*>(e->pref[e->cur]) + e->rflag_off : nullptr;
+    p.rflag_in =
+        e->facts.rflag_ok[e->cur] ? reinterpret_cast<const uint8_t*>(e->pref[e->cur]) + e->rflag_off : nullptr;
   }
   // uniform rows: sweep rounds at k = 8 tag the snapshot they write; a round whose input snapshot
   // is known uniform tests settled tiles with no peer draw and no gather (kernels.h uni_*)
-  // (a node-sharded engine sees every row only through the peer exchange, whose pushes carry the slots)
-  // (unsynced_shard, diagnostics: a rank's share alone, on its own slot: timing as in a peer-push run)
-  bool uni = e->uni_rows && sweep && e->k == 8 && !replay && !e->comm && !e->ablate_gather &&
-             (e->NL == (uint32_t)e->N || e->peer_world > 1 || e->unsynced_shard);
-  if (uni) {
-    int rc = ref_pick(e);
-    if (rc != AV_OK) return rc;
-    uni = e->ref_node >= 0;
-  }
-  if (uni) {
+  if (plan.uni_rows) {
     p.ref_node = (uint32_t)e->ref_node;
     p.uni_off = (uint32_t)e->uni_off;
     p.uni_world = (uint32_t)std::max(1, e->peer_world);
     p.uni_rank = (uint32_t)std::max(0, e->peer_rank);
     p.uni_out = e->pref[nb] + e->uni_off;
-    p.uni_in = e->uni_ok[e->cur] ? e->pref[e->cur] + e->uni_off : nullptr;
+    p.uni_in = e->facts.uni_ok[e->cur] ? e->pref[e->cur] + e->uni_off : nullptr;
     const int pv = av_engine::prv(e->cur);
-    p.uni_prev = e->uni_ok[pv] ? e->pref[pv] + e->uni_off : nullptr;
+    p.uni_prev = e->facts.uni_ok[pv] ? e->pref[pv] + e->uni_off : nullptr;
     p.uni_merge = e->uni_merge;
-    p.uni_post = peer && sweep && !replay ? 1u : 0u;  // the slot reaches the peers in the barrier kernel
+    p.uni_post = p.push_n ? 1u : 0u;  // the slot reaches the peers in the barrier kernel
   }
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (e->warm_pref && sweep) {  // diagnostics (untimed): the round's gather sources, read once
-    if (!e->touch_sink) AV_HIP(hipMalloc(&e->touch_sink, 64));
-    AV_HIP(avk::launch_touch(p.pref_prev, (size_t)e->N * e->PS * 4u, e->touch_sink, e->stream));
-    AV_HIP(avk::launch_touch(p.pref_in, (size_t)e->N * e->PS * 4u, e->touch_sink, e->stream));
-  }
-  if (e->timing) {
-    AV_HIP(hipEventCreate(&ev0));
-    AV_HIP(hipEventCreate(&ev1));
-    AV_HIP(hipEventRecord(ev0, e->stream));
-  }
-  if (p.push_n && e->masked) {  // (inside the round's timing: the exchange's own work)
-    int rc = need_combine(e, e->round / avk::kNeedWin);
-    if (rc == AV_OK) rc = need_draw_ahead(e, e->round / avk::kNeedWin + 1);
-    if (rc != AV_OK) return rc;
-  }
-  bool refw = false;  // the round wrote reference-row flags for the snapshot it published
-  if (sweep)
-    AV_HIP(avk::launch_round_sweep(p, e->k, replay != nullptr, e->sweep_blocks, e->stream, &refw));
-  else if (e->kernel == 2 && e->k <= 8 && e->capped && !compat) {
-    p.node_flags = e->node_flags;
-    AV_HIP(avk::launch_round_node(p, e->k, replay != nullptr, /*exact_pass=*/e->count_bound >= 120, e->stream));
-  }
-  else
-    AV_HIP(avk::launch_round(p, e->k, replay != nullptr, e->capped, e->stream));
-  if (e->pub_mode == 2) {  // the responders' re-adds (main.go:175-177)
-    AV_HIP(avk::launch_readd(p, e->stream));
-    e->warm_all = false;
-    e->count_bound = 127;
-  }
-  e->count_bound = std::min(127, e->count_bound + e->k);
-  if (fresh && p.hivirt) e->k_pend = true;  // the fresh round flags its tiles kHiVirt
-  e->fresh = false;
-  e->rflag_ok[nb] = refr && refw;
-  e->uni_ok[nb] = uni;
-  if (replay)
-    e->warm_all = false;
-  else if (e->c_monotone && e->k >= 8 && !e->capped && all_valid)
-    e->warm_all = true;  // every live record was polled and shifted in 8 considered votes
+  return AV_OK;
+}
+
+// The pair of events around one timed launch (av_set_timing; av_kernel_stats sums them).
+int timing_begin(av_engine* e, hipEvent_t* ev0, hipEvent_t* ev1) {
+  if (!e->timing) return AV_OK;
+  AV_HIP(hipEventCreate(ev0));
+  AV_HIP(hipEventCreate(ev1));
+  AV_HIP(hipEventRecord(*ev0, e->stream));
+  return AV_OK;
+}
+
+int timing_end(av_engine* e, hipEvent_t ev0, hipEvent_t ev1) {
+  AV_HIP(hipEventRecord(ev1, e->stream));
+  e->events.emplace_back(ev0, ev1);
+  return AV_OK;
+}
+
+// What follows a round's kernel: the next window's need masks (inside the round's timing), then this
+// rank's rows of buffer nb to the peers where the kernel did not push them, the barrier, the RCCL
+// all-gather.
+int exchange_tail(av_engine* e, const avk::RoundParams& p, int nb, hipEvent_t ev0, hipEvent_t ev1) {
+  const bool peer = e->peer_world > 1;
   if (peer) {
     // the next push round's window drawn and pushed before the barrier (combined after it)
-    int rc = need_gen(e, (e->round + 1) / avk::kNeedWin);
-    if (rc != AV_OK) return rc;
+    AV_TRY(need_gen(e, (e->round + 1) / avk::kNeedWin));
   }
-  if (e->timing) {
-    AV_HIP(hipEventRecord(ev1, e->stream));
-    e->events.emplace_back(ev0, ev1);
+  if (ev0) {
+    AV_TRY(timing_end(e, ev0, ev1));
   } else if (e->round_marker) {  // diagnostics: a timing-free event after every round
     if (!e->marker) AV_HIP(hipEventCreateWithFlags(&e->marker, hipEventDisableTiming));
     AV_HIP(hipEventRecord(e->marker, e->stream));
   }
   if (peer) {
     if (!p.push_n) {
-      int rc = push_own_rows(e, nb);
-      if (rc == AV_OK) rc = stale_clear(e, nb);
-      if (rc != AV_OK) return rc;
+      AV_TRY(push_own_rows(e, nb));
+      AV_TRY(stale_clear(e, nb));
     }
-    int rc = peer_barrier(e, p.uni_post ? nb : -1);
-    if (rc != AV_OK) return rc;
+    AV_TRY(peer_barrier(e, p.uni_post ? nb : -1));
   } else if (e->solo_barrier) {
-    int rc = peer_barrier(e);
-    if (rc != AV_OK) return rc;
+    AV_TRY(peer_barrier(e));
   }
   if (e->comm) {
     const size_t count = (size_t)e->NL * e->PS;
-    uint32_t* out = e->pref[av_engine::nxt(e->cur)];
+    uint32_t* out = e->pref[nb];
     ncclResult_t r = ncclAllGather(out + (size_t)e->n0 * e->PS, out, count, ncclUint32, e->comm, e->stream);
     AV_CHECK(r == ncclSuccess, AV_ERR_RCCL, "ncclAllGather: %s", ncclGetErrorString(r));
   }
-  e->cur = av_engine::nxt(e->cur);
+  return AV_OK;
+}
+
+int launch_one_round(av_engine* e, const uint32_t* replay) {
+  AV_TRY(round_checks(e, 1));
+  avk::RoundPlan plan = plan_for(e, replay != nullptr);
+  AV_CHECK(!plan.unsupported, AV_ERR_UNSUPPORTED,
+           "the example responder and av_set_polling need M <= 4096 (uncapped)");
+  AV_TRY(materialize(e, plan.wb_votes, false));  // (two passes, votes first)
+  AV_TRY(materialize(e, false, plan.wb_counts));
+  avk::RoundParams p = round_params(e, replay);
+  p.vv = plan.vv ? 1u : 0u;
+  p.vv_uniform = plan.vv_uniform ? 1u : 0u;
+  p.fresh = plan.fresh ? 1u : 0u;
+  p.klazy = plan.klazy ? 1u : 0u;
+  p.kconsume = plan.kconsume ? 1u : 0u;
+  p.hivirt = plan.hivirt ? 1u : 0u;
+  const bool sweep = plan.kernel == avk::RoundKernel::Sweep;
+  const int nb = av_engine::nxt(e->cur);
+  fill_push_params(e, sweep && !replay, nb, p);
+  AV_TRY(fill_row_params(e, plan, nb, p));
+  if (e->warm_pref && sweep) {  // diagnostics (untimed): the round's gather sources, read once
+    if (!e->touch_sink) AV_HIP(hipMalloc(&e->touch_sink, 64));
+    AV_HIP(avk::launch_touch(p.pref_prev, (size_t)e->N * e->PS * 4u, e->touch_sink, e->stream));
+    AV_HIP(avk::launch_touch(p.pref_in, (size_t)e->N * e->PS * 4u, e->touch_sink, e->stream));
+  }
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  AV_TRY(timing_begin(e, &ev0, &ev1));
+  if (p.push_n && e->masked) {  // (inside the round's timing: the exchange's own work)
+    AV_TRY(need_combine(e, e->round / avk::kNeedWin));
+    AV_TRY(need_draw_ahead(e, e->round / avk::kNeedWin + 1));
+  }
+  bool refw = false;  // the round wrote reference-row flags for the snapshot it published
+  switch (plan.kernel) {
+    case avk::RoundKernel::Sweep:
+      AV_HIP(avk::launch_round_sweep(p, e->k, plan.mode, e->sweep_blocks, e->stream, &refw));
+      break;
+    case avk::RoundKernel::Node:
+      p.node_flags = e->node_flags;
+      AV_HIP(avk::launch_round_node(p, e->k, plan.replay, plan.exact_pass, e->stream));
+      break;
+    case avk::RoundKernel::FirstGen:
+      AV_HIP(avk::launch_round(p, e->k, plan.replay, e->capped, e->stream));
+      break;
+  }
+  if (e->pub_mode == 2) {  // the responders' re-adds (main.go:175-177)
+    AV_HIP(avk::launch_readd(p, e->stream));
+    e->facts.responder_readds();
+  }
+  e->facts.after_round(plan, all_targets_valid(e), refw, nb);
+  AV_TRY(exchange_tail(e, p, nb, ev0, ev1));
+  e->cur = nb;
   e->round++;
   return AV_OK;
 }
@@ -896,13 +837,10 @@ int launch_one_round(av_engine* e, const uint32_t* replay) {
 // launch, followed per round by the exact pass over the nodes it left at that
 // round (count >= 120). Host-side round bookkeeping as launch_one_round.
 int launch_replay_fused(av_engine* e, const uint32_t* replay0, int32_t R) {
-  if (e) ref_invalidate(e);
-  AV_CHECK(e->round + R - 1 - e->log_base < e->max_log_rounds(), AV_ERR_OVERFLOW,
-           "StatusUpdate log spans %lld rounds: call av_fetch_updates more often", (long long)e->max_log_rounds());
-  int rc = materialize_votes_only(e);
-  if (rc != AV_OK) return rc;
-  rc = materialize_counts(e);
-  if (rc != AV_OK) return rc;
+  e->facts.snapshot_written();
+  AV_TRY(round_checks(e, R));
+  AV_TRY(materialize(e, true, false));
+  AV_TRY(materialize(e, false, true));
   const size_t per = e->round_replay_words();
   avk::RoundParams p = round_params(e, replay0);
   p.node_flags = e->node_flags;
@@ -912,30 +850,22 @@ int launch_replay_fused(av_engine* e, const uint32_t* replay0, int32_t R) {
   p.ring_next = (uint32_t)av_engine::nxt(e->cur);
   for (int i = 0; i < 3; ++i) p.pref_ring[i] = e->pref[i];
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (e->timing) {
-    AV_HIP(hipEventCreate(&ev0));
-    AV_HIP(hipEventCreate(&ev1));
-    AV_HIP(hipEventRecord(ev0, e->stream));
-  }
+  AV_TRY(timing_begin(e, &ev0, &ev1));
   AV_HIP(avk::launch_replay_node(p, e->k, e->stream));
   for (int32_t r = 0; r < R; ++r) {
-    if (e->count_bound >= 120) {  // a node may have reached count 120 by this round
+    const avk::RoundPlan plan = plan_for(e, true);
+    if (plan.exact_pass) {  // a node may have reached count 120 by this round
       avk::RoundParams q = round_params(e, replay0 + per * (size_t)r);
       q.node_flags = e->node_flags;
       q.exact_rel = (uint32_t)r;
       q.exact_keep = r + 1 < R ? 1u : 0u;
       AV_HIP(avk::launch_round(q, e->k, /*replay=*/true, /*capped=*/true, e->stream));
     }
-    e->count_bound = std::min(127, e->count_bound + e->k);
-    e->fresh = false;
-    e->warm_all = false;
     e->cur = av_engine::nxt(e->cur);
+    e->facts.after_round(plan, /*all_valid: not read after a replay round*/ false, false, e->cur);
     e->round++;
   }
-  if (e->timing) {
-    AV_HIP(hipEventRecord(ev1, e->stream));
-    e->events.emplace_back(ev0, ev1);
-  }
+  if (ev0) return timing_end(e, ev0, ev1);
   return AV_OK;
 }
 
@@ -983,15 +913,11 @@ uint32_t default_sweep_blocks(const av_engine* e, bool force = false) {
 // Waves that write the StatusUpdate log in the fewest-wave round kernel the engine may launch: every
 // writer picks shard wave % log_shards, so with more shards than writers the rest would sit empty and
 // the usable capacity shrink by that factor. Capped engines: k_round_node (one wave per node per 64
-// blocks); uncapped: the sweep grid's waves that own a run of tiles (launch_sweep_k: runs of
-// ceil(tiles / waves) tiles), never more than the tiles (the first-generation kernels: one per tile).
+// blocks); uncapped: the sweep grid's waves that own a run of tiles (round_plan.h sweep_grid, shared
+// with launch_sweep_k), never more than the tiles (the first-generation kernels: one per tile).
 uint64_t log_writer_waves(const av_engine* e) {
   if (e->capped) return (uint64_t)e->NL * ((e->BL + 63) / 64);
-  const uint64_t tiles = e->Lpad / 64;
-  if (!e->sweep_blocks) return tiles;
-  const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>(e->sweep_blocks, (tiles + 3) / 4));
-  const uint64_t run = (tiles + grid * 4 - 1) / (grid * 4);
-  return std::max<uint64_t>(1, (tiles + run - 1) / run);
+  return avk::sweep_run_waves(e->Lpad / 64, e->sweep_blocks);
 }
 
 // Shard count and per-shard capacities of the (empty) log from the allocation and the writers: a
@@ -1037,7 +963,7 @@ int alloc_arrival(av_engine* e) {
 }
 
 int refresh_pref(av_engine* e) {
-  ref_invalidate(e);
+  e->facts.snapshot_written();
   AV_HIP(avk::launch_refresh_pref((uint32_t)e->pub_mode, e->planes, e->pref[e->cur], e->byz, (uint32_t)e->n0, e->NL,
                                   e->BL, e->PS, (uint32_t)e->round, e->stream));
   return AV_OK;
@@ -1291,22 +1217,12 @@ int av_create(const av_config* cfg, av_engine** out) {
 }
 
 int av_init_records(av_engine* e, int32_t init_mode, uint32_t init_param) {
-  if (e) ref_invalidate(e);
   AV_ENTER(e);
-  e->warm_all = false;
-  // every record starts at count 0 with no considered vote (NewVoteRecord, vote.go:33-35), and a
-  // count step needs > 6 considered votes in the 8-vote window (vote.go:58-61): the first 6 votes
-  // of a fresh record cannot step it, so after v votes every count is <= v - 6
-  e->count_bound = -6;
-  if (e->v_stale) {  // every plane is rewritten
-    AV_HIP(hipMemsetAsync(e->vstale, 0, (size_t)(e->Lpad / 64) * 4, e->stream));
-    e->v_stale = false;
-  }
-  if (e->k_pend) {
-    AV_HIP(hipMemsetAsync(e->kpend, 0, (size_t)(e->Lpad / 64) * 4, e->stream));
-    e->k_pend = false;
-  }
   AV_CHECK(init_mode >= AV_INIT_NONE && init_mode <= AV_INIT_PAIRS, AV_ERR_INVALID_ARG, "bad init_mode");
+  // every plane is rewritten: nothing deferred survives
+  if (e->facts.v_stale) AV_HIP(hipMemsetAsync(e->vstale, 0, (size_t)(e->Lpad / 64) * 4, e->stream));
+  if (e->facts.k_pend) AV_HIP(hipMemsetAsync(e->kpend, 0, (size_t)(e->Lpad / 64) * 4, e->stream));
+  e->facts.init(init_mode != AV_INIT_NONE);
   avk::InitParams p{};
   p.planes = e->planes;
   p.pref = e->pref[e->cur];
@@ -1330,29 +1246,21 @@ int av_init_records(av_engine* e, int32_t init_mode, uint32_t init_param) {
     // peer-push engine: this rank's new rows of the current snapshot go to every peer replica, and
     // no rank's next round may read them before all ranks have pushed (collective: every rank
     // re-initialises). The other two buffers are untouched, so their replicas stay identical.
-    int rc = push_own_rows(e, e->cur);
-    if (rc == AV_OK) rc = stale_clear(e, e->cur);
-    if (rc == AV_OK) rc = need_gen(e, e->round / avk::kNeedWin);
-    if (rc != AV_OK) return rc;
-    rc = peer_barrier(e);
-    if (rc != AV_OK) return rc;
-  }
-  e->fresh = init_mode != AV_INIT_NONE;
-  // lanes of the padded tail of the last tile hold no records
-  if (e->Lpad > e->L) {
-    // padded lanes are never loaded (active = g < L), nothing to do
+    AV_TRY(push_own_rows(e, e->cur));
+    AV_TRY(stale_clear(e, e->cur));
+    AV_TRY(need_gen(e, e->round / avk::kNeedWin));
+    AV_TRY(peer_barrier(e));
   }
   AV_HIP(hipStreamSynchronize(e->stream));
   return AV_OK;
 }
 
 int av_set_valid(av_engine* e, int64_t target, int32_t valid) {
-  if (e) ref_invalidate(e);
+  if (e) e->facts.snapshot_written();
   AV_ENTER(e);
   AV_CHECK(target >= 0 && target < e->M, AV_ERR_INVALID_ARG, "target out of range");
   if (!local_target(e, target)) return AV_OK;
-  int rc = materialize_votes(e);  // stale tiles must not gain live-but-invalid records
-  if (rc != AV_OK) return rc;
+  AV_TRY(materialize_votes(e));  // stale tiles must not gain live-but-invalid records
   const int64_t tl = target - e->t0;
   const uint32_t b = (uint32_t)(tl >> 5), m = 1u << (tl & 31);
   e->valid_host[b] = valid ? (e->valid_host[b] | m) : (e->valid_host[b] & ~m);
@@ -1363,20 +1271,13 @@ int av_set_valid(av_engine* e, int64_t target, int32_t valid) {
 
 int av_add_targets(av_engine* e, int64_t node, const int64_t* targets, const uint8_t* accepted, int64_t n,
                    uint8_t* added) {
-  if (e) ref_invalidate(e);
+  if (e) e->facts.snapshot_written();
   AV_ENTER(e);
-  {
-    int rc = peer_local_write_check(e);
-    if (rc != AV_OK) return rc;
-  }
+  AV_TRY(peer_local_write_check(e));
   AV_CHECK(n >= 0 && (n == 0 || (targets && accepted && added)), AV_ERR_INVALID_ARG, "null argument");
   AV_CHECK(local_node(e, node), AV_ERR_INVALID_ARG, "node %lld not in this shard", (long long)node);
-  {
-    int rc = materialize_votes(e);
-    if (rc != AV_OK) return rc;
-  }
-  e->warm_all = false;
-  e->fresh = false;
+  AV_TRY(materialize_votes(e));
+  e->facts.add_targets();
   std::vector<uint32_t> tl;
   std::vector<uint8_t> acc;
   std::vector<int64_t> pos;
@@ -1484,12 +1385,9 @@ int av_register_votes(av_engine* e, int64_t node, const int64_t* targets, const 
 // u32 errs are never copied as such).
 int av_register_votes_batch(av_engine* e, int64_t n_resp, const int64_t* nodes, const int64_t* offsets,
                             const int64_t* targets, const uint32_t* errs, int32_t* status_out) {
-  if (e) ref_invalidate(e);
+  if (e) e->facts.snapshot_written();
   AV_ENTER(e);
-  {
-    int rc = peer_local_write_check(e);
-    if (rc != AV_OK) return rc;
-  }
+  AV_TRY(peer_local_write_check(e));
   AV_CHECK(n_resp >= 0 && (n_resp == 0 || (nodes && offsets)), AV_ERR_INVALID_ARG, "null argument");
   if (n_resp == 0) return AV_OK;
   AV_CHECK(n_resp < (1ll << 31), AV_ERR_INVALID_ARG, "too many Responses in one call");
@@ -1502,11 +1400,7 @@ int av_register_votes_batch(av_engine* e, int64_t n_resp, const int64_t* nodes, 
   AV_CHECK(n == 0 || (targets && errs && status_out), AV_ERR_INVALID_ARG, "null argument");
   AV_CHECK(n < (1ll << 31), AV_ERR_INVALID_ARG, "too many votes in one call");
   AV_CHECK(e->t1 - e->t0 <= (int64_t)avk::kDropTl + 1, AV_ERR_UNSUPPORTED, "drop-in votes need <= 4M local targets");
-  {
-    int rc = materialize_votes(e);
-    if (rc != AV_OK) return rc;
-  }
-  e->fresh = false;
+  AV_TRY(materialize_votes(e));
   // at most one confidence step per vote: bound by the most votes one node gets; the Responses
   // grouped by node, in call order inside a group (fast path)
   int64_t max_node_votes = 0;
@@ -1529,15 +1423,14 @@ int av_register_votes_batch(av_engine* e, int64_t n_resp, const int64_t* nodes, 
     grp_off.push_back((uint32_t)n_resp);
   }
   const uint32_t n_groups = (uint32_t)grp_off.size() - 1u;
-  e->count_bound = (int)std::min<int64_t>(127, e->count_bound + max_node_votes);
-  if (n == 0) return AV_OK;
+  if (n == 0) {
+    e->facts.dropin_votes(max_node_votes, false);
+    return AV_OK;
+  }
   // ---- pack (pinned): votes, then the Response table
   const size_t tab_words = 2 * (size_t)n_resp + 1 + (size_t)n_resp + n_groups + 1;  // off, node, order, grp_off
   const size_t hb = (size_t)n * 5 + tab_words * 4 + 64;
-  {
-    int rc = dropin_staging(e, hb);
-    if (rc != AV_OK) return rc;
-  }
+  AV_TRY(dropin_staging(e, hb));
   auto* hpack = static_cast<uint32_t*>(e->dropin_host);
   auto* hoff = hpack + n;
   auto* hnode = hoff + n_resp + 1;
@@ -1565,11 +1458,12 @@ int av_register_votes_batch(av_engine* e, int64_t n_resp, const int64_t* nodes, 
     asc_t[t] = asc;
     neutral_t[t] = neutral;
   });
-  bool ascending = true;
+  bool ascending = true, neutral = false;
   for (int t = 0; t < 64; ++t) {
     ascending &= asc_t[t] != 0;
-    if (neutral_t[t]) e->c_monotone = false;  // a neutral vote shifts in consider = 0
+    neutral |= neutral_t[t] != 0;
   }
+  e->facts.dropin_votes(max_node_votes, neutral);
   const bool fast = ascending && e->dropin_fast;
   // ---- device: packed votes + Response table + byte statuses (+ grouping scratch)
   size_t tb = 0;
@@ -1585,8 +1479,7 @@ int av_register_votes_batch(av_engine* e, int64_t n_resp, const int64_t* nodes, 
   const size_t head_words = (size_t)m + tab_words + ((size_t)m + 3) / 4;
   const size_t grp_words = fast ? 0 : 8 * (size_t)m + ((size_t)m + 1) + 1 + 2 * (size_t)m;
   void* buf = nullptr;
-  int rc = engine_scratch(e, (head_words + grp_words) * 4 + tb + 512, &buf);
-  if (rc != AV_OK) return rc;
+  AV_TRY(engine_scratch(e, (head_words + grp_words) * 4 + tb + 512, &buf));
   auto* w = static_cast<uint32_t*>(buf);
   uint32_t *dpack = w, *doff = dpack + m, *dnode = doff + n_resp + 1, *dorder = dnode + n_resp,
            *dgrp = dorder + n_resp;
@@ -1650,11 +1543,10 @@ int av_read_records(av_engine* e, int64_t n0, int64_t n1, int64_t t0, int64_t t1
   // the deferred forms (stale vote planes, pending count steps) are read
   // through, not written back: a read leaves the next round's fast paths on
   avk::RoundParams p = round_params(e, nullptr);
-  p.vv = e->v_stale ? 1u : 0u;
-  p.klazy = e->k_pend ? 1u : 0u;
+  p.vv = e->facts.v_stale ? 1u : 0u;
+  p.klazy = e->facts.k_pend ? 1u : 0u;
   void* buf = nullptr;
-  int rc = engine_scratch(e, n * 4, &buf);
-  if (rc != AV_OK) return rc;
+  AV_TRY(engine_scratch(e, n * 4, &buf));
   AV_HIP(avk::launch_read_records_virtual(p, (uint32_t)(n0 - e->n0), (uint32_t)(n1 - e->n0), (uint32_t)(t0 - e->t0),
                                           (uint32_t)(t1 - e->t0), static_cast<uint32_t*>(buf), e->stream));
   AV_HIP(hipMemcpyAsync(out, buf, n * 4, hipMemcpyDeviceToHost, e->stream));
@@ -1664,31 +1556,22 @@ int av_read_records(av_engine* e, int64_t n0, int64_t n1, int64_t t0, int64_t t1
 }
 
 int av_write_records(av_engine* e, int64_t n0, int64_t n1, int64_t t0, int64_t t1, const uint32_t* in) {
-  if (e) ref_invalidate(e);
+  if (e) e->facts.snapshot_written();
   AV_ENTER(e);
-  {
-    int rc = peer_local_write_check(e);
-    if (rc != AV_OK) return rc;
-  }
+  AV_TRY(peer_local_write_check(e));
   AV_CHECK(in && n0 >= e->n0 && n0 <= n1 && n1 <= e->n1 && t0 >= e->t0 && t0 <= t1 && t1 <= e->t1,
            AV_ERR_INVALID_ARG, "range outside this engine's shard");
-  {
-    int rc = materialize_votes(e);
-    if (rc != AV_OK) return rc;
-  }
+  AV_TRY(materialize_votes(e));
   const size_t n = (size_t)(n1 - n0) * (size_t)(t1 - t0);
   if (!n) return AV_OK;
-  e->c_monotone = false;
-  e->fresh = false;
-  e->count_bound = 127;  // arbitrary counts written
+  e->facts.write_records();
   Scratch s;
   AV_HIP(s.ensure(n * 4));
   AV_HIP(hipMemcpyAsync(s.p, in, n * 4, hipMemcpyHostToDevice, e->stream));
   AV_HIP(avk::launch_write_records(e->planes, e->BL, (uint32_t)(n0 - e->n0), (uint32_t)(n1 - e->n0),
                                    (uint32_t)(t0 - e->t0), (uint32_t)(t1 - e->t0), static_cast<uint32_t*>(s.p),
                                    e->stream));
-  int rc = refresh_pref(e);
-  if (rc != AV_OK) return rc;
+  AV_TRY(refresh_pref(e));
   AV_HIP(hipStreamSynchronize(e->stream));
   return AV_OK;
 }
@@ -1698,8 +1581,7 @@ int av_is_accepted(av_engine* e, int64_t node, int64_t target, int32_t* out) {
   *out = 0;
   if (!local_node(e, node) || !local_target(e, target)) return AV_OK;  // no record -> false
   uint32_t w = 0;
-  int rc = av_read_records(e, node, node + 1, target, target + 1, &w);
-  if (rc != AV_OK) return rc;
+  AV_TRY(av_read_records(e, node, node + 1, target, target + 1, &w));
   if (((w >> 17) < (uint32_t)AV_FINALIZATION_SCORE)) *out = (int32_t)((w >> 16) & 1u);
   return AV_OK;
 }
@@ -1708,8 +1590,7 @@ int av_get_confidence(av_engine* e, int64_t node, int64_t target, uint16_t* out)
   AV_CHECK(e && out, AV_ERR_INVALID_ARG, "null argument");
   if (!local_node(e, node) || !local_target(e, target)) return fail(AV_ERR_NOT_FOUND, "VoteRecord not found");
   uint32_t w = 0;
-  int rc = av_read_records(e, node, node + 1, target, target + 1, &w);
-  if (rc != AV_OK) return rc;
+  AV_TRY(av_read_records(e, node, node + 1, target, target + 1, &w));
   if ((w >> 17) >= (uint32_t)AV_FINALIZATION_SCORE) return fail(AV_ERR_NOT_FOUND, "VoteRecord not found");
   *out = (uint16_t)(w >> 17);
   return AV_OK;
@@ -1720,8 +1601,7 @@ int av_get_invs(av_engine* e, int64_t node, int64_t* out_targets, int64_t cap, i
   *n_out = 0;
   AV_CHECK(local_node(e, node), AV_ERR_INVALID_ARG, "node not in this shard");
   std::vector<uint32_t> w((size_t)(e->t1 - e->t0));
-  int rc = av_read_records(e, node, node + 1, e->t0, e->t1, w.data());
-  if (rc != AV_OK) return rc;
+  AV_TRY(av_read_records(e, node, node + 1, e->t0, e->t1, w.data()));
   int64_t cnt = 0;
   for (int64_t tl = 0; tl < (int64_t)w.size() && cnt < AV_MAX_ELEMENT_POLL; ++tl) {
     const bool live = (w[tl] >> 17) < (uint32_t)AV_FINALIZATION_SCORE;
@@ -1764,8 +1644,7 @@ int av_get_invs_batch(av_engine* e, int64_t n0, int64_t n1, int64_t* offsets, in
   auto* hoffs = static_cast<int64_t*>(e->invs_host);
   auto* doffs = static_cast<int64_t*>(dev_view);
   void* scratch = nullptr;
-  int rc = engine_scratch(e, (size_t)avk::poll_sets_scratch_words(n) * 8, &scratch);
-  if (rc != AV_OK) return rc;
+  AV_TRY(engine_scratch(e, (size_t)avk::poll_sets_scratch_words(n) * 8, &scratch));
   AV_HIP(avk::launch_poll_sets_batch(e->planes, e->valid, e->BL, (uint32_t)(n0 - e->n0), n, (uint32_t)e->t0, keep,
                                      static_cast<uint64_t*>(scratch), doffs, reinterpret_cast<int32_t*>(doffs + n + 1),
                                      e->stream));
@@ -1782,8 +1661,7 @@ int av_run_rounds(av_engine* e, int32_t rounds) {
   AV_PEER_CHECK(e);
   AV_CHECK(rounds >= 0, AV_ERR_INVALID_ARG, "rounds < 0");
   for (int32_t r = 0; r < rounds; ++r) {
-    int rc = launch_one_round(e, nullptr);
-    if (rc != AV_OK) return rc;
+    AV_TRY(launch_one_round(e, nullptr));
   }
   return AV_OK;
 }
@@ -1792,7 +1670,7 @@ int av_replay_round_errs(av_engine* e, const uint32_t* errs) {
   AV_ENTER(e);
   AV_PEER_CHECK(e);
   AV_CHECK(errs, AV_ERR_INVALID_ARG, "null argument");
-  e->c_monotone = false;
+  e->facts.replay_call();
   const int64_t TL = e->t1 - e->t0;
   std::vector<uint32_t> planes(e->round_replay_words(), 0u);
   for (uint32_t nl = 0; nl < e->NL; ++nl)
@@ -1815,8 +1693,7 @@ int av_replay_round_errs(av_engine* e, const uint32_t* errs) {
   Scratch s;
   AV_HIP(s.ensure(planes.size() * 4));
   AV_HIP(hipMemcpyAsync(s.p, planes.data(), planes.size() * 4, hipMemcpyHostToDevice, e->stream));
-  int rc = launch_one_round(e, static_cast<uint32_t*>(s.p));
-  if (rc != AV_OK) return rc;
+  AV_TRY(launch_one_round(e, static_cast<uint32_t*>(s.p)));
   AV_HIP(hipStreamSynchronize(e->stream));
   return AV_OK;
 }
@@ -1849,7 +1726,7 @@ int av_replay_rounds(av_engine* e, int32_t rounds) {
   AV_CHECK(rounds >= 0, AV_ERR_INVALID_ARG, "rounds < 0");
   AV_CHECK(e->round >= e->replay_first && e->round + rounds <= e->replay_first + e->replay_ready,
            AV_ERR_INVALID_ARG, "replay stream not prepared for these rounds");
-  if (rounds > 0) e->c_monotone = false;
+  if (rounds > 0) e->facts.replay_call();
   const size_t per = e->round_replay_words();
   // capped engines (poll cap binds) fuse consecutive replay rounds: every node's
   // records depend only on its own stream (k_replay_node)
@@ -1858,8 +1735,7 @@ int av_replay_rounds(av_engine* e, int32_t rounds) {
   for (int32_t r = 0; r < rounds;) {
     const uint32_t* rp = e->replay + per * (size_t)(e->round - e->replay_first);
     const int32_t n = fuse ? std::min<int32_t>(rounds - r, e->replay_fuse) : 1;
-    int rc = n > 1 ? launch_replay_fused(e, rp, n) : launch_one_round(e, rp);
-    if (rc != AV_OK) return rc;
+    AV_TRY(n > 1 ? launch_replay_fused(e, rp, n) : launch_one_round(e, rp));
     r += n;
   }
   return AV_OK;
@@ -1894,7 +1770,7 @@ int av_set_round(av_engine* e, int64_t node, int64_t round) {
 }
 
 int av_set_polling(av_engine* e, int64_t node, int32_t polls) {
-  if (e) ref_invalidate(e);
+  if (e) e->facts.snapshot_written();
   AV_ENTER(e);
   AV_CHECK(local_node(e, node), AV_ERR_INVALID_ARG, "node %lld not in this shard", (long long)node);
   AV_CHECK(e->peer_world <= 1, AV_ERR_UNSUPPORTED, "av_set_polling on a peer-push engine");
@@ -1905,8 +1781,7 @@ int av_set_polling(av_engine* e, int64_t node, int32_t polls) {
   const uint32_t nl = (uint32_t)(node - e->n0);
   uint32_t& w = e->nopoll_host[nl >> 5];
   w = polls ? (w & ~(1u << (nl & 31))) : (w | (1u << (nl & 31)));
-  int rc = materialize_votes(e);  // rounds of non-polling networks run the first-generation kernel
-  if (rc != AV_OK) return rc;
+  AV_TRY(materialize_votes(e));  // rounds of non-polling networks run the first-generation kernel
   AV_HIP(hipMemcpyAsync(e->nopoll, e->nopoll_host.data(), e->nopoll_host.size() * 4, hipMemcpyHostToDevice,
                         e->stream));
   AV_HIP(hipStreamSynchronize(e->stream));
@@ -2003,8 +1878,7 @@ int read_log_counts(av_engine* e, LogCounts& c) {
 // (every enqueued round has finished: read_log_counts synchronizes), else at the next clear_log.
 int relayout_log_if_empty(av_engine* e) {
   LogCounts c;
-  int rc = read_log_counts(e, c);
-  if (rc != AV_OK) return rc;
+  AV_TRY(read_log_counts(e, c));
   if (!c.ovf && c.total == 0 && c.n_singles == 0 && c.n_med == 0 && c.n_records == 0) set_log_layout(e);
   return AV_OK;
 }
@@ -2040,12 +1914,10 @@ int copy_out_bytes(av_engine* e, void* out, const void* dev, size_t n) {
     AV_HIP(hipEventRecord(e->stage_ev[c & 1], e->stream));
     return AV_OK;
   };
-  int rc = dma(0);
-  if (rc != AV_OK) return rc;
+  AV_TRY(dma(0));
   for (size_t c = 0; c < chunks; ++c) {
     if (c + 1 < chunks) {
-      rc = dma(c + 1);  // its staging buffer's previous chunk (c - 1) was copied out already
-      if (rc != AV_OK) return rc;
+      AV_TRY(dma(c + 1));  // its staging buffer's previous chunk (c - 1) was copied out already
     }
     AV_HIP(hipEventSynchronize(e->stage_ev[c & 1]));
     const size_t w = std::min(kChunk, n - c * kChunk);
@@ -2126,8 +1998,7 @@ int encode_log(av_engine* e, const LogCounts& c, bool compact, void* dev, Encode
   AV_CHECK(entries < (1ull << 40), AV_ERR_UNSUPPORTED, "StatusUpdate log too large to order");
   p.nr = per;
   void* scratch = nullptr;
-  int rc = engine_scratch(e, avk::encode_scratch_bytes(p, entries, per * e->NL), &scratch);
-  if (rc != AV_OK) return rc;
+  AV_TRY(engine_scratch(e, avk::encode_scratch_bytes(p, entries, per * e->NL), &scratch));
   const uint32_t chunks = (e->NL + kChunkNodes - 1) / kChunkNodes;
   auto* base = static_cast<uint8_t*>(dev);
   uint64_t* cidx = compact ? reinterpret_cast<uint64_t*>(base + kHdrBytes) : nullptr;
@@ -2199,11 +2070,9 @@ int grow_pinned(void** p, size_t* have, size_t want) {
 
 // Read the log's counters, failing (and clearing the log) if it overflowed.
 int pending_counts(av_engine* e, LogCounts& c) {
-  int rc = read_log_counts(e, c);
-  if (rc != AV_OK) return rc;
+  AV_TRY(read_log_counts(e, c));
   if (c.ovf) {
-    rc = clear_log(e);
-    if (rc != AV_OK) return rc;
+    AV_TRY(clear_log(e));
     return fail(AV_ERR_OVERFLOW, "device StatusUpdate log overflowed (%lld updates, capacity %lld per shard)",
                 (long long)c.total, (long long)e->log_cap);
   }
@@ -2225,11 +2094,9 @@ int av_fetch_updates(av_engine* e, uint64_t* out, int64_t cap, int64_t* n_out) {
   if (c.total > 0) {
     // the compact slots' device buffers hold no in-flight copy source after this wait
     if (e->copy_stream) AV_HIP(hipStreamSynchronize(e->copy_stream));
-    rc = grow_dev(&e->cdev[0], &e->cdev_bytes[0], (size_t)c.total * 8);
-    if (rc != AV_OK) return rc;
+    AV_TRY(grow_dev(&e->cdev[0], &e->cdev_bytes[0], (size_t)c.total * 8));
     Encoded r;
-    rc = encode_log(e, c, false, e->cdev[0], &r);
-    if (rc != AV_OK) return rc;
+    AV_TRY(encode_log(e, c, false, e->cdev[0], &r));
     rc = copy_out(e, out, static_cast<const uint64_t*>(e->cdev[0]), (size_t)c.total);
     if (rc != AV_OK) return rc;
   }
@@ -2242,20 +2109,16 @@ int av_fetch_compact(av_engine* e, void* out, int64_t cap, int64_t* bytes) {
   AV_CHECK(bytes && (cap == 0 || out), AV_ERR_INVALID_ARG, "null argument");
   *bytes = 0;
   LogCounts c;
-  int rc = pending_counts(e, c);
-  if (rc != AV_OK) return rc;
+  AV_TRY(pending_counts(e, c));
   if (e->copy_stream) AV_HIP(hipStreamSynchronize(e->copy_stream));
   const avk::EncodeParams p = encode_params(e);
-  rc = grow_dev(&e->cdev[0], &e->cdev_bytes[0], compact_bound(e, p, c));
-  if (rc != AV_OK) return rc;
+  AV_TRY(grow_dev(&e->cdev[0], &e->cdev_bytes[0], compact_bound(e, p, c)));
   Encoded r;
-  rc = encode_log(e, c, true, e->cdev[0], &r);
-  if (rc != AV_OK) return rc;
+  AV_TRY(encode_log(e, c, true, e->cdev[0], &r));
   *bytes = r.bytes;
   AV_CHECK(r.bytes <= cap, AV_ERR_OVERFLOW, "cap too small: the stream takes %lld bytes", (long long)r.bytes);
-  rc = copy_out_bytes(e, static_cast<uint8_t*>(out) + kHdrBytes, static_cast<const uint8_t*>(e->cdev[0]) + kHdrBytes,
-                      (size_t)r.bytes - kHdrBytes);
-  if (rc != AV_OK) return rc;
+  AV_TRY(copy_out_bytes(e, static_cast<uint8_t*>(out) + kHdrBytes,
+                        static_cast<const uint8_t*>(e->cdev[0]) + kHdrBytes, (size_t)r.bytes - kHdrBytes));
   std::memcpy(out, &r.hdr, kHdrBytes);
   return clear_log(e);
 }
@@ -2268,21 +2131,17 @@ int av_fetch_compact_async(av_engine* e, int64_t* ticket) {
   const int s = (int)(e->cticket % av_engine::kSlots);
   if (!e->cev[s]) AV_HIP(hipEventCreateWithFlags(&e->cev[s], hipEventDisableTiming));
   LogCounts c;
-  int rc = pending_counts(e, c);  // waits for the rounds enqueued before
-  if (rc != AV_OK) return rc;
+  AV_TRY(pending_counts(e, c));  // waits for the rounds enqueued before
   // the slot's previous copy (ticket - kSlots) has read its device buffer and filled its host buffer
   if (e->cpend[s]) AV_HIP(hipEventSynchronize(e->cev[s]));
   e->cpend[s] = false;
   const avk::EncodeParams p = encode_params(e);
   e->cdev_hwm = std::max(e->cdev_hwm, compact_bound(e, p, c));
-  rc = grow_dev(&e->cdev[s], &e->cdev_bytes[s], e->cdev_hwm);
-  if (rc != AV_OK) return rc;
+  AV_TRY(grow_dev(&e->cdev[s], &e->cdev_bytes[s], e->cdev_hwm));
   Encoded r;
-  rc = encode_log(e, c, true, e->cdev[s], &r);  // synchronizes the engine stream
-  if (rc != AV_OK) return rc;
+  AV_TRY(encode_log(e, c, true, e->cdev[s], &r));  // synchronizes the engine stream
   e->chost_hwm = std::max(e->chost_hwm, (size_t)r.bytes + 16);
-  rc = grow_pinned(&e->chost[s], &e->chost_bytes[s], e->chost_hwm);
-  if (rc != AV_OK) return rc;
+  AV_TRY(grow_pinned(&e->chost[s], &e->chost_bytes[s], e->chost_hwm));
   if (e->copy_blocks) {  // a small copy kernel (the header's bytes are copied too, and overwritten on wait)
     void* hdev = nullptr;
     AV_HIP(hipHostGetDevicePointer(&hdev, e->chost[s], 0));
@@ -2471,13 +2330,12 @@ int av_census(av_engine* e, int64_t n0, int64_t n1, int32_t honest_only, const a
   // [256] histogram, the nodes counted, one pad word; then the node rows (16-byte aligned)
   const size_t head = tn * 4 + 256 + 2, head_bytes = head * 8;
   void* buf = nullptr;
-  int rc = engine_scratch(e, head_bytes + (out->node_classes ? nn * 16 : 0), &buf);
-  if (rc != AV_OK) return rc;
+  AV_TRY(engine_scratch(e, head_bytes + (out->node_classes ? nn * 16 : 0), &buf));
   AV_HIP(hipMemsetAsync(buf, 0, head_bytes + (out->node_classes ? nn * 16 : 0), e->stream));
   auto* d = static_cast<unsigned long long*>(buf);
   avk::CensusParams p{};
   p.planes = e->planes;
-  p.kpend = e->k_pend ? e->kpend : nullptr;
+  p.kpend = e->facts.k_pend ? e->kpend : nullptr;
   p.valid = e->valid;
   p.byz = e->byz;
   p.tcls = out->target_classes ? d : nullptr;
@@ -2524,8 +2382,7 @@ int av_log_entries(av_engine* e, int64_t out[3]) {
   AV_PEER_SYNC_CHECK(e);
   AV_CHECK(out, AV_ERR_INVALID_ARG, "null argument");
   LogCounts c;
-  int rc = read_log_counts(e, c);
-  if (rc != AV_OK) return rc;
+  AV_TRY(read_log_counts(e, c));
   out[0] = c.n_singles;
   out[1] = c.n_med;
   out[2] = c.n_records;
@@ -2537,8 +2394,7 @@ int av_resize_log(av_engine* e, const int64_t entries[3]) {
   AV_PEER_SYNC_CHECK(e);
   AV_CHECK(entries && entries[0] >= 0 && entries[1] >= 0 && entries[2] >= 0, AV_ERR_INVALID_ARG, "bad entries");
   LogCounts c;
-  int rc = read_log_counts(e, c);
-  if (rc != AV_OK) return rc;
+  AV_TRY(read_log_counts(e, c));
   AV_CHECK(!c.ovf && c.total == 0 && c.n_singles == 0 && c.n_med == 0 && c.n_records == 0, AV_ERR_UNSUPPORTED,
            "av_resize_log: the log holds updates (fetch or discard them first)");
   // sized for the current grid's writer waves (log_writer_waves): a shard takes every sh-th writer, so
@@ -2613,18 +2469,9 @@ int av_materialize(av_engine* e) {
   AV_ENTER(e);
   AV_PEER_CHECK(e);
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (e->timing && (e->v_stale || e->k_pend)) {
-    AV_HIP(hipEventCreate(&ev0));
-    AV_HIP(hipEventCreate(&ev1));
-    AV_HIP(hipEventRecord(ev0, e->stream));
-  }
-  int rc = materialize_votes(e);
-  if (rc != AV_OK) return rc;
-  if (ev0) {
-    AV_HIP(hipEventRecord(ev1, e->stream));
-    e->events.emplace_back(ev0, ev1);
-  }
-  return AV_OK;
+  if (e->facts.v_stale || e->facts.k_pend) AV_TRY(timing_begin(e, &ev0, &ev1));
+  AV_TRY(materialize_votes(e));
+  return ev0 ? timing_end(e, ev0, ev1) : AV_OK;
 }
 
 int av_read_pref(av_engine* e, int64_t n0, int64_t n1, int64_t t0, int64_t t1, uint8_t* out) {
@@ -2674,185 +2521,225 @@ int av_sample_peers(av_engine* e, int64_t round, int64_t n0, int64_t n1, int32_t
   return AV_OK;
 }
 
-int av_set_option(av_engine* e, const char* name, int64_t value) {
-  if (e) ref_invalidate(e);
-  AV_CHECK(e && name, AV_ERR_INVALID_ARG, "null argument");
-  const std::string n(name);
-  if (n == "plane_nt") {
-    e->plane_nt = value != 0;
-  } else if (n == "ablate_phase") {  // diagnostics (kernels.h RoundParams::ablate_phase; results invalid)
-    e->ablate_phase = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(31, value));
-  } else if (n == "ablate_emit") {
-    e->ablate_emit = (int)std::max<int64_t>(0, std::min<int64_t>(3, value));
-  } else if (n == "k_hi_virtual") {  // A/B: virtual K4..K7 group (kernels.h kHiVirt)
-    int rc = materialize_counts(e);
-    if (rc != AV_OK) return rc;
-    e->k_hi_virtual = value != 0;
-  } else if (n == "uni_merge") {  // tuning: runs per wave in a uniform-input round (1 = off)
-    AV_CHECK(value >= 1 && value <= 16, AV_ERR_INVALID_ARG, "bad uni_merge");
-    e->uni_merge = (uint32_t)value;
-  } else if (n == "uniform_rows") {  // A/B: uniform-row settled tests (kernels.h uni_*)
-    e->uni_rows = value != 0;
-    ref_invalidate(e);
-  } else if (n == "ref_rows") {  // reference-row flags in converged sweep rounds (kernels.h)
-    e->ref_rows = value != 0;
-  } else if (n == "replay_fuse") {  // replay rounds per fused launch on capped engines (<= 1: one launch per round)
-    AV_CHECK(value >= 0 && value <= 4096, AV_ERR_INVALID_ARG, "replay_fuse must be in [0, 4096]");
-    e->replay_fuse = (int)value;
-  } else if (n == "ablate_node") {
-    e->ablate_node = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(7, value));
-  } else if (n == "ablate_gather") {
-    e->ablate_gather = value != 0;
-  } else if (n == "kernel") {  // 2 = k_round_sweep (default where it applies), 1 = k_round_fast
-    AV_CHECK(value == 1 || value == 2, AV_ERR_INVALID_ARG, "kernel must be 1 or 2");
-    e->kernel = (int)value;
-  } else if (n == "store_policy") {
-    AV_CHECK(value >= 0 && value <= 3, AV_ERR_INVALID_ARG, "store_policy must be in [0, 3]");
-    e->store_policy = (uint32_t)value;
-  } else if (n == "sweep_blocks") {  // 0 = one wave per tile, -1 = the default choice, -2 = resident grid
-    AV_CHECK(value >= -2 && value < (1ll << 31), AV_ERR_INVALID_ARG, "bad sweep_blocks");
-    if (value < 0) {
-      AV_ENTER(e);
-      e->sweep_blocks = default_sweep_blocks(e, value == -2);
-      e->sweep_blocks_explicit = false;
-    } else {
-      e->sweep_blocks = (uint32_t)value;
-      e->sweep_blocks_explicit = true;
-    }
-    AV_ENTER(e);
-    int rc = relayout_log_if_empty(e);
-    if (rc != AV_OK) return rc;
-  } else if (n == "settled_fast") {
-    e->settled_fast = value != 0;
-  } else if (n == "replay_fast") {
-    e->replay_fast = value != 0;
-  } else if (n == "count_changed") {  // diagnostics: count changed published words in every sweep round
-    e->count_changed = value != 0;
-  } else if (n == "solo_barrier") {  // diagnostics: a one-rank barrier after every round (exchange_cost.py)
-    AV_CHECK(e->peer_world <= 1 && !e->comm, AV_ERR_UNSUPPORTED, "solo_barrier: engine has an exchange");
-    if (value && !e->arrive) {
-      AV_ENTER(e);
-      int rc = alloc_arrival(e);
-      if (rc != AV_OK) return rc;
-      e->peer_arrive.p[0] = e->arrive;
-    }
-    e->solo_barrier = value != 0;
-    e->solo_used = e->solo_used || e->solo_barrier;
-  } else if (n == "copy_blocks") {
-    AV_CHECK(value >= 0 && value <= 4096, AV_ERR_INVALID_ARG, "copy_blocks must be in [0, 4096]");
-    e->copy_blocks = (uint32_t)value;
-  } else if (n == "enc_buckets") {  // (round, node) buckets per encoder pass (tests of the multi-pass path)
-    AV_CHECK(value >= 1 && value <= (1ll << 30), AV_ERR_INVALID_ARG, "enc_buckets must be in [1, 2^30]");
-    e->enc_buckets = (uint32_t)value;
-  } else if (n == "dropin_fast") {
-    e->dropin_fast = value != 0;
-  } else if (n == "settled_lean") {
-    e->settled_lean = value != 0;
-  } else if (n == "wave_runs") {
-    e->wave_runs = value != 0;
-  } else if (n == "sweep_nopipe") {
-    e->sweep_nopipe = value != 0;
-  } else if (n == "tiles_per_wave") {
-    AV_CHECK(value >= 0 && value <= 4096, AV_ERR_INVALID_ARG, "bad tiles_per_wave");
-    e->tiles_per_wave = (uint32_t)value;
-    // the default grid depends on the run length; an explicit sweep_blocks stays as set
-    if (!e->sweep_blocks_explicit) e->sweep_blocks = default_sweep_blocks(e);
-    AV_ENTER(e);
-    int rc = relayout_log_if_empty(e);
-    if (rc != AV_OK) return rc;
-  } else if (n == "unsynced_shard") {
-    e->unsynced_shard = value != 0;
-  } else if (n == "warm_pref") {
-    e->warm_pref = value != 0;
-  } else if (n == "round_marker") {
-    e->round_marker = value != 0;
-  } else if (n == "virtual_votes") {  // 0: always store the vote planes (A/B)
-    e->virtual_votes = value != 0;
-  } else if (n == "count_lazy") {  // 0: always store the count planes (A/B)
-    AV_ENTER(e);
-    int rc = materialize_counts(e);
-    if (rc != AV_OK) return rc;
-    e->count_lazy = value != 0;
-  } else if (n == "vv_min_bl") {
-    AV_CHECK(value >= 1 && value < (1ll << 31), AV_ERR_INVALID_ARG, "bad vv_min_bl");
-    e->vv_min_bl = (uint32_t)value;
-  } else if (n == "responder") {  // 0 = R2 decision, 1 = IsAccepted literally, 2 = the example's responder
-    AV_ENTER(e);
-    AV_CHECK(value >= 0 && value <= 2, AV_ERR_INVALID_ARG, "responder must be 0, 1 or 2");
-    AV_CHECK(value != 2 || (e->NL == (uint32_t)e->N && e->t0 == 0 && e->t1 == e->M && e->peer_world <= 1 && !e->comm),
-             AV_ERR_UNSUPPORTED, "the example responder (re-adds) needs an unsharded engine");
-    AV_CHECK(value == 0 || e->peer_world <= 1, AV_ERR_UNSUPPORTED, "responder variants on a peer-push engine");
-    if (value == 2 && !e->readd) {
-      AV_HIP(dev_alloc(&e->readd, e->L));
-      AV_HIP(dev_alloc(&e->died_out, e->L));
-      AV_HIP(hipMemsetAsync(e->readd, 0, (size_t)e->L * 4, e->stream));
-      AV_HIP(hipMemsetAsync(e->died_out, 0, (size_t)e->L * 4, e->stream));
-    }
-    int rc = materialize_votes(e);
-    if (rc != AV_OK) return rc;
-    e->pub_mode = (int32_t)value;
-    rc = refresh_pref(e);  // republish the current snapshot under the new rule
-    if (rc != AV_OK) return rc;
-    AV_HIP(hipStreamSynchronize(e->stream));
-  } else if (n == "uni_votes") {
-    e->uni_votes = value != 0 ? 1u : 0u;
-  } else if (n == "quiet_tiles") {  // A/B: quiescent settled tiles skip the A read and the republish
-    e->quiet_tiles = value != 0 ? 1u : 0u;
-  } else if (n == "wave_dense") {  // A/B: the dense log must hold one record per lane with updates
-    AV_CHECK(value >= 0 && value <= 64, AV_ERR_INVALID_ARG, "bad wave_dense");
-    e->wave_dense = (uint32_t)value;
-  } else if (n == "dense_min") {  // tuning (A/B): fewer updates per dense record; the dense log may fill sooner
-    AV_CHECK(value >= 1 && value <= 32 * (int64_t)e->k + 1, AV_ERR_INVALID_ARG, "bad dense_min");
-    e->dense_min = (uint32_t)value;
-  } else if (n == "fresh") {  // 0: a round after init reads every plane (A/B only)
-    if (!value) e->fresh = false;
-  } else if (n == "push_defer") {  // A/B: 0 = every push stored from the tile loop
-    e->push_defer = value != 0;
-  } else if (n == "tile_draw") {  // A/B: per-tile shared peer draws in runs whose nodes overflow the run's draw
-    AV_CHECK(value == 0 || value == 1, AV_ERR_INVALID_ARG, "tile_draw must be 0 or 1");
-    e->tile_draw = (uint32_t)value;
-  } else if (n == "materialize_run") {  // A/B: tiles per wave of the deferred state's write-back
-    AV_CHECK(value >= 1 && value <= 64, AV_ERR_INVALID_ARG, "materialize_run must be 1..64");
-    e->mat_run = (uint32_t)value;
-  } else if (n == "census_blocks") {  // workgroups of av_census's grid (0 = the engine's choice)
-    AV_CHECK(value >= 0 && value <= 65536, AV_ERR_INVALID_ARG, "census_blocks must be in [0, 65536]");
-    e->census_blocks = (uint32_t)value;
-  } else if (n == "push_store") {  // A/B: 1 = plain stores (default), 0 = system scope, 2 = none (results invalid)
-    AV_CHECK(value >= 0 && value <= 2, AV_ERR_INVALID_ARG, "push_store must be 0, 1 or 2");
-    e->push_store = (uint32_t)value;
-  } else if (n == "peer_mask") {  // before the exchange is set up: need-masked pushes (default 1)
-    AV_CHECK(e->peer_world == 0, AV_ERR_INVALID_ARG, "peer_mask must be set before the exchange is set up");
-    e->peer_mask = value != 0;
-  } else if (n == "pref_uncached") {
-    // A/B: the three snapshot buffers re-allocated uncached (hipDeviceMallocUncached: the L2 does not
-    // keep their lines, a gather reads the bytes it asks for instead of a 128-B line fill) or back
-    AV_CHECK(value == 0 || value == 1, AV_ERR_INVALID_ARG, "pref_uncached must be 0 or 1");
-    AV_CHECK(!e->arrive && !e->group, AV_ERR_UNSUPPORTED, "pref_uncached: not with a peer exchange");
-    if ((value != 0) != e->pref_uncached) {
-      AV_HIP(hipStreamSynchronize(e->stream));
-      for (int b = 0; b < 3; ++b) {
-        uint32_t* nb = nullptr;
-        AV_HIP(hipExtMallocWithFlags(reinterpret_cast<void**>(&nb), e->pref_alloc_words * 4,
-                                     value ? hipDeviceMallocUncached : hipDeviceMallocDefault));
-        AV_HIP(hipMemcpy(nb, e->pref[b], e->pref_alloc_words * 4, hipMemcpyDeviceToDevice));
-        AV_HIP(hipFree(e->pref[b]));
-        e->pref[b] = nb;
-      }
-      e->pref_uncached = value != 0;
-    }
-  } else if (n == "peer_fine") {  // before av_peer_handles: fine-grained snapshot buffers (default 1)
-    AV_CHECK(!e->arrive, AV_ERR_INVALID_ARG, "peer_fine must be set before av_peer_handles");
-    e->peer_fine = value != 0;
-  } else if (n == "barrier_timeout_ms") {
-    AV_CHECK(value >= 1 && value <= 3600000, AV_ERR_INVALID_ARG, "bad barrier_timeout_ms");
-    e->barrier_timeout_ms = (uint32_t)value;
-    e->barrier_ticks = 0;  // recomputed at the next barrier
-  } else if (n == "warm_skip") {  // may only be switched off (it is a proven invariant, not a hint)
-    if (!value) e->c_monotone = false;
-  } else {
-    return fail(AV_ERR_INVALID_ARG, "unknown option '%s'", name);
-  }
+}  // extern "C"
+
+namespace {
+
+// ---- av_set_option (documented in include/avhip.h) ----
+// Plain options only store a value: a bool (value != 0), or an integer in [lo, hi] that is rejected
+// (AV_ERR_INVALID_ARG) or clamped outside it.
+enum OptKind { kBool, kReject, kClamp };
+struct PlainOption {
+  const char* name;
+  OptKind kind;
+  int64_t lo, hi;
+  bool av_engine::*b;  // the member: one of the three
+  uint32_t av_engine::*u;
+  int av_engine::*i;
+};
+constexpr PlainOption opt(const char* n, bool av_engine::*m) { return {n, kBool, 0, 1, m, nullptr, nullptr}; }
+constexpr PlainOption opt(const char* n, uint32_t av_engine::*m, OptKind kd = kBool, int64_t lo = 0, int64_t hi = 1) {
+  return {n, kd, lo, hi, nullptr, m, nullptr};
+}
+constexpr PlainOption opt(const char* n, int av_engine::*m, OptKind kd, int64_t lo, int64_t hi) {
+  return {n, kd, lo, hi, nullptr, nullptr, m};
+}
+
+constexpr PlainOption kPlainOptions[] = {
+    opt("plane_nt", &av_engine::plane_nt),              // non-temporal plane loads / stores
+    opt("uniform_rows", &av_engine::uni_rows),          // A/B: uniform-row settled tests (kernels.h uni_*)
+    opt("ref_rows", &av_engine::ref_rows),              // reference-row flags in converged sweep rounds (kernels.h)
+    opt("virtual_votes", &av_engine::virtual_votes),    // 0: always store the vote planes (A/B)
+    opt("vv_min_bl", &av_engine::vv_min_bl, kReject, 1, (1ll << 31) - 1),  // smallest BL with stale votes
+    opt("kernel", &av_engine::kernel, kReject, 1, 2),  // 2 = k_round_sweep / k_round_node, 1 = k_round_fast
+    opt("store_policy", &av_engine::store_policy, kReject, 0, 3),  // 2 = sc1 plane stores, 3 = nt sc1
+    opt("settled_fast", &av_engine::settled_fast),      // settled warm tiles skip the round step's bookkeeping
+    opt("settled_lean", &av_engine::settled_lean),      // a run's settled candidates tested in one lean loop
+    opt("wave_runs", &av_engine::wave_runs),            // a wave takes a run of tiles and draws their peers once
+    opt("sweep_nopipe", &av_engine::sweep_nopipe),      // 0 = the prefetching kModeWarmPipe on a resident grid (A/B)
+    opt("uni_merge", &av_engine::uni_merge, kReject, 1, 16),  // runs per wave, uniform-input rounds
+    opt("uni_votes", &av_engine::uni_votes),            // uniform input: the reference word as every tile's votes
+    opt("quiet_tiles", &av_engine::quiet_tiles),        // A/B: quiescent settled tiles skip the A read and the republish
+    opt("wave_dense", &av_engine::wave_dense, kReject, 0, 64),  // A/B: dense records per wave (0 off)
+    opt("tile_draw", &av_engine::tile_draw, kReject, 0, 1),  // A/B: per-tile shared draws in overflowing runs
+    opt("materialize_run", &av_engine::mat_run, kReject, 1, 64),  // A/B: tiles per wave of the write-back
+    opt("replay_fuse", &av_engine::replay_fuse, kReject, 0, 4096),  // replay rounds per launch (<= 1: off)
+    opt("replay_fast", &av_engine::replay_fast),        // k_replay_fast where the poll set is the first 128 lanes
+    opt("dropin_fast", &av_engine::dropin_fast),        // 0: drop-in batches always take the sort-grouped path
+    opt("push_defer", &av_engine::push_defer),          // A/B: 0 = every push stored from the tile loop
+    opt("push_store", &av_engine::push_store, kReject, 0, 2),  // A/B: 0 = system scope, 2 = none (invalid)
+    opt("census_blocks", &av_engine::census_blocks, kReject, 0, 65536),  // av_census grid (0 = by size)
+    opt("copy_blocks", &av_engine::copy_blocks, kReject, 0, 4096),  // stream copy kernel (0 = runtime copy)
+    opt("enc_buckets", &av_engine::enc_buckets, kReject, 1, 1ll << 30),  // buckets per encoder pass
+    opt("count_changed", &av_engine::count_changed),    // diagnostics: count changed published words in every sweep round
+    opt("round_marker", &av_engine::round_marker),      // diagnostics: a timing-free event after every round
+    opt("warm_pref", &av_engine::warm_pref),            // diagnostics: the gather sources read once before a timed round
+    opt("unsynced_shard", &av_engine::unsynced_shard),  // diagnostics (invalid results): rounds with no exchange
+    opt("ablate_gather", &av_engine::ablate_gather),    // diagnostics (invalid results)
+    opt("ablate_phase", &av_engine::ablate_phase, kClamp, 0, 31),  // diagnostics (kernels.h; invalid results)
+    opt("ablate_emit", &av_engine::ablate_emit, kClamp, 0, 3),     // diagnostics (invalid results)
+    opt("ablate_node", &av_engine::ablate_node, kClamp, 0, 7),     // diagnostics (k_round_node)
+};
+
+int opt_range(const char* name, int64_t value, int64_t lo, int64_t hi) {
+  AV_CHECK(value >= lo && value <= hi, AV_ERR_INVALID_ARG, "%s must be in [%lld, %lld]", name, (long long)lo,
+           (long long)hi);
   return AV_OK;
+}
+
+int set_plain(av_engine* e, const PlainOption& o, int64_t value) {
+  if (o.kind == kReject) AV_TRY(opt_range(o.name, value, o.lo, o.hi));
+  value = o.kind == kBool ? value != 0 : std::max(o.lo, std::min(o.hi, value));
+  if (o.b)
+    e->*o.b = value != 0;
+  else if (o.u)
+    e->*o.u = (uint32_t)value;
+  else
+    e->*o.i = (int)value;
+  return AV_OK;
+}
+
+// Options with side effects. Every handler that touches the device enters through AV_ENTER.
+// 0 = one wave per tile, -1 = the default choice, -2 = resident grid
+int opt_sweep_blocks(av_engine* e, int64_t value) {
+  AV_TRY(opt_range("sweep_blocks", value, -2, (1ll << 31) - 1));
+  AV_ENTER(e);
+  e->sweep_blocks = value < 0 ? default_sweep_blocks(e, value == -2) : (uint32_t)value;
+  e->sweep_blocks_explicit = value >= 0;
+  return relayout_log_if_empty(e);
+}
+
+int opt_tiles_per_wave(av_engine* e, int64_t value) {
+  AV_TRY(opt_range("tiles_per_wave", value, 0, 4096));
+  AV_ENTER(e);
+  e->tiles_per_wave = (uint32_t)value;
+  // the default grid depends on the run length; an explicit sweep_blocks stays as set
+  if (!e->sweep_blocks_explicit) e->sweep_blocks = default_sweep_blocks(e);
+  return relayout_log_if_empty(e);
+}
+
+// diagnostics: a one-rank barrier after every round (exchange_cost.py)
+int opt_solo_barrier(av_engine* e, int64_t value) {
+  AV_CHECK(e->peer_world <= 1 && !e->comm, AV_ERR_UNSUPPORTED, "solo_barrier: engine has an exchange");
+  if (value && !e->arrive) {
+    AV_ENTER(e);
+    AV_TRY(alloc_arrival(e));
+    e->peer_arrive.p[0] = e->arrive;
+  }
+  e->solo_barrier = value != 0;
+  e->solo_used = e->solo_used || e->solo_barrier;
+  return AV_OK;
+}
+
+// "count_lazy" (0: always store the count planes) and "k_hi_virtual" (the virtual K4..K7 group, kernels.h
+// kHiVirt), A/B: what is deferred under the old setting is written back
+template <bool av_engine::*M>
+int opt_count_planes(av_engine* e, int64_t value) {
+  AV_ENTER(e);
+  AV_TRY(materialize(e, false, true));
+  e->*M = value != 0;
+  return AV_OK;
+}
+
+// 0 = R2 decision, 1 = IsAccepted literally, 2 = the example's responder
+int opt_responder(av_engine* e, int64_t value) {
+  AV_ENTER(e);
+  AV_CHECK(value >= 0 && value <= 2, AV_ERR_INVALID_ARG, "responder must be 0, 1 or 2");
+  AV_CHECK(value != 2 || (e->NL == (uint32_t)e->N && e->t0 == 0 && e->t1 == e->M && e->peer_world <= 1 && !e->comm),
+           AV_ERR_UNSUPPORTED, "the example responder (re-adds) needs an unsharded engine");
+  AV_CHECK(value == 0 || e->peer_world <= 1, AV_ERR_UNSUPPORTED, "responder variants on a peer-push engine");
+  if (value == 2 && !e->readd) {
+    AV_HIP(dev_alloc(&e->readd, e->L));
+    AV_HIP(dev_alloc(&e->died_out, e->L));
+    AV_HIP(hipMemsetAsync(e->readd, 0, (size_t)e->L * 4, e->stream));
+    AV_HIP(hipMemsetAsync(e->died_out, 0, (size_t)e->L * 4, e->stream));
+  }
+  AV_TRY(materialize_votes(e));
+  e->pub_mode = (int32_t)value;
+  AV_TRY(refresh_pref(e));  // republish the current snapshot under the new rule
+  AV_HIP(hipStreamSynchronize(e->stream));
+  return AV_OK;
+}
+
+// A/B: the three snapshot buffers re-allocated uncached (hipDeviceMallocUncached: the L2 does not
+// keep their lines, a gather reads the bytes it asks for instead of a 128-B line fill) or back
+int opt_pref_uncached(av_engine* e, int64_t value) {
+  AV_TRY(opt_range("pref_uncached", value, 0, 1));
+  AV_CHECK(!e->arrive && !e->group, AV_ERR_UNSUPPORTED, "pref_uncached: not with a peer exchange");
+  if ((value != 0) == e->pref_uncached) return AV_OK;
+  AV_ENTER(e);
+  AV_HIP(hipStreamSynchronize(e->stream));
+  for (int b = 0; b < 3; ++b) {
+    uint32_t* nb = nullptr;
+    AV_HIP(hipExtMallocWithFlags(reinterpret_cast<void**>(&nb), e->pref_alloc_words * 4,
+                                 value ? hipDeviceMallocUncached : hipDeviceMallocDefault));
+    AV_HIP(hipMemcpy(nb, e->pref[b], e->pref_alloc_words * 4, hipMemcpyDeviceToDevice));
+    AV_HIP(hipFree(e->pref[b]));
+    e->pref[b] = nb;
+  }
+  e->pref_uncached = value != 0;
+  return AV_OK;
+}
+
+constexpr struct {
+  const char* name;
+  int (*set)(av_engine*, int64_t);
+} kOptionHandlers[] = {
+    {"sweep_blocks", opt_sweep_blocks},
+    {"tiles_per_wave", opt_tiles_per_wave},
+    {"solo_barrier", opt_solo_barrier},
+    {"count_lazy", opt_count_planes<&av_engine::count_lazy>},
+    {"k_hi_virtual", opt_count_planes<&av_engine::k_hi_virtual>},
+    {"responder", opt_responder},
+    {"pref_uncached", opt_pref_uncached},
+    // 0: a round after init reads every plane (A/B only)
+    {"fresh", [](av_engine* e, int64_t v) -> int {
+       if (!v) e->facts.option_fresh_off();
+       return AV_OK;
+     }},
+    // may only be switched off (it is a proven invariant, not a hint)
+    {"warm_skip", [](av_engine* e, int64_t v) -> int {
+       if (!v) e->facts.option_warm_skip_off();
+       return AV_OK;
+     }},
+    // before the exchange is set up: need-masked pushes (default 1)
+    {"peer_mask", [](av_engine* e, int64_t v) -> int {
+       AV_CHECK(e->peer_world == 0, AV_ERR_INVALID_ARG, "peer_mask must be set before the exchange is set up");
+       e->peer_mask = v != 0;
+       return AV_OK;
+     }},
+    // before av_peer_handles: fine-grained snapshot buffers (default 1)
+    {"peer_fine", [](av_engine* e, int64_t v) -> int {
+       AV_CHECK(!e->arrive, AV_ERR_INVALID_ARG, "peer_fine must be set before av_peer_handles");
+       e->peer_fine = v != 0;
+       return AV_OK;
+     }},
+    {"barrier_timeout_ms", [](av_engine* e, int64_t v) -> int {
+       AV_TRY(opt_range("barrier_timeout_ms", v, 1, 3600000));
+       e->barrier_timeout_ms = (uint32_t)v;
+       e->barrier_ticks = 0;  // recomputed at the next barrier
+       return AV_OK;
+     }},
+    // tuning (A/B): fewer updates per dense record; the dense log may fill sooner
+    {"dense_min", [](av_engine* e, int64_t v) -> int {
+       AV_TRY(opt_range("dense_min", v, 1, 32 * (int64_t)e->k + 1));
+       e->dense_min = (uint32_t)v;
+       return AV_OK;
+     }},
+};
+
+}  // namespace
+
+extern "C" {
+
+int av_set_option(av_engine* e, const char* name, int64_t value) {
+  if (e) e->facts.snapshot_written();
+  AV_CHECK(e && name, AV_ERR_INVALID_ARG, "null argument");
+  for (const PlainOption& o : kPlainOptions)
+    if (!std::strcmp(name, o.name)) return set_plain(e, o, value);
+  for (const auto& h : kOptionHandlers)
+    if (!std::strcmp(name, h.name)) return h.set(e, value);
+  return fail(AV_ERR_INVALID_ARG, "unknown option '%s'", name);
 }
 
 int av_set_timing(av_engine* e, int32_t enable) {
@@ -2901,7 +2788,7 @@ int av_comm_unique_id(uint8_t out[128]) {
 }
 
 int av_comm_init(av_engine* e, int32_t world, int32_t rank, const uint8_t id[128]) {
-  if (e) ref_invalidate(e);
+  if (e) e->facts.snapshot_written();
   AV_ENTER(e);
   AV_CHECK(id && world >= 1 && rank >= 0 && rank < world, AV_ERR_INVALID_ARG, "bad world/rank");
   AV_CHECK(e->N % world == 0 && (int64_t)e->NL * world == e->N && e->n0 == (int64_t)rank * e->NL,
@@ -2947,8 +2834,7 @@ int av_peer_handles(av_engine* e, uint8_t out[AV_PEER_HANDLE_BYTES]) {
         e->pref[b] = fine;
       }
     }
-    int rc = alloc_arrival(e);
-    if (rc != AV_OK) return rc;
+    AV_TRY(alloc_arrival(e));
   }
   void* bufs[4] = {e->pref[0], e->pref[1], e->pref[2], e->arrive};
   for (int i = 0; i < 4; ++i) {
@@ -2964,7 +2850,7 @@ int av_peer_handles(av_engine* e, uint8_t out[AV_PEER_HANDLE_BYTES]) {
 }
 
 int av_peer_init(av_engine* e, int32_t world, int32_t rank, const uint8_t* handles) {
-  if (e) ref_invalidate(e);
+  if (e) e->facts.snapshot_written();
   AV_ENTER(e);
   AV_CHECK(handles && world >= 1 && world <= avk::kMaxPeers + 1 && rank >= 0 && rank < world, AV_ERR_INVALID_ARG,
            "bad world/rank (at most %d ranks)", avk::kMaxPeers + 1);
@@ -3026,14 +2912,11 @@ int av_peer_init(av_engine* e, int32_t world, int32_t rank, const uint8_t* handl
     // every replica of every snapshot buffer identical from here on: each
     // rank pushes its own rows of the three buffers, then all ranks meet
     for (int b = 0; b < 3; ++b) {
-      int rc = push_own_rows(e, b);
-      if (rc != AV_OK) return rc;
+      AV_TRY(push_own_rows(e, b));
     }
-    int rc = mask_setup(e);
-    if (rc == AV_OK) rc = need_gen(e, e->round / avk::kNeedWin);
-    if (rc != AV_OK) return rc;
-    rc = peer_barrier(e);
-    if (rc != AV_OK) return rc;
+    AV_TRY(mask_setup(e));
+    AV_TRY(need_gen(e, e->round / avk::kNeedWin));
+    AV_TRY(peer_barrier(e));
   }
   return av_synchronize(e);
 }
@@ -3081,7 +2964,7 @@ int av_peer_group_serial(av_engine** engines, int32_t world) {
   g->alive = world;
   for (int r = 0; r < world; ++r) {
     av_engine* e = engines[r];
-    ref_invalidate(e);
+    e->facts.snapshot_written();
     e->group = g;
     e->own_stream = e->stream;
     e->stream = g->stream;
@@ -3107,12 +2990,10 @@ int av_peer_group_serial(av_engine** engines, int32_t world) {
   // every replica of every snapshot buffer identical from here on
   for (int r = 0; r < world; ++r) {
     for (int b = 0; b < 3; ++b) {
-      int rc = push_own_rows(engines[r], b);
-      if (rc != AV_OK) return rc;
+      AV_TRY(push_own_rows(engines[r], b));
     }
-    int rc = mask_setup(engines[r]);
-    if (rc == AV_OK) rc = need_gen(engines[r], engines[r]->round / avk::kNeedWin);
-    if (rc != AV_OK) return rc;
+    AV_TRY(mask_setup(engines[r]));
+    AV_TRY(need_gen(engines[r], engines[r]->round / avk::kNeedWin));
   }
   AV_HIP(hipStreamSynchronize(g->stream));
   return AV_OK;
@@ -3122,10 +3003,9 @@ int av_peer_sync(av_engine* e) {
   AV_ENTER(e);
   AV_PEER_CHECK(e);
   if (e->peer_world <= 1) return AV_OK;
-  int rc = push_own_rows(e, e->cur);
-  if (rc == AV_OK) rc = stale_clear(e, e->cur);
-  if (rc == AV_OK) rc = peer_barrier(e);
-  if (rc != AV_OK) return rc;
+  AV_TRY(push_own_rows(e, e->cur));
+  AV_TRY(stale_clear(e, e->cur));
+  AV_TRY(peer_barrier(e));
   AV_HIP(hipStreamSynchronize(e->stream));
   return peer_failed(e);
 }

@@ -256,7 +256,7 @@ constexpr uint32_t kPendAllLive = 0x80000000u;
 // engine's last target (k_init_planes: every existing target's record live, none deleted since).
 // Set by the fresh round; kept by a warm round whose counts all stay < 16 with no deletion (or
 // that defers the tile's count planes); written back by the round that breaks it, kconsume and
-// k_kl_materialize (k_read_records_v reads it virtually).
+// k_materialize (k_read_records_v reads it virtually).
 constexpr uint32_t kHiVirt = 0x40000000u;
 __host__ __device__ inline uint32_t real_mask(uint32_t tn, uint32_t b) {  // existing targets of local block b
   const uint32_t rem = tn > b * 32u ? tn - b * 32u : 0u;
@@ -325,8 +325,10 @@ hipError_t launch_round(const RoundParams& p, int k, bool replay, bool capped, h
 hipError_t launch_replay_node(const RoundParams& p, int k, hipStream_t s);
 // Persistent streaming round kernel (round_sweep.hip), uncapped path, k <= 8:
 // `blocks` workgroups of 256 threads sweep the tiles; 0 = one wave per tile.
+// mode: the round plan's (round_plan.h plan_round)
 // ref_written (may be null): whether the launch wrote p.rflag_out (only the walking warm mode does)
-hipError_t launch_round_sweep(const RoundParams& p, int k, bool replay, uint32_t blocks, hipStream_t s,
+enum class SweepMode : int;
+hipError_t launch_round_sweep(const RoundParams& p, int k, SweepMode mode, uint32_t blocks, hipStream_t s,
                               bool* ref_written = nullptr);
 // Capped round (M > 4096, k <= 8; round_node.hip): one workgroup per node;
 // nodes that may finalize a record this round are flagged in p.node_flags and
@@ -335,13 +337,10 @@ hipError_t launch_round_sweep(const RoundParams& p, int k, bool replay, uint32_t
 hipError_t launch_round_node(const RoundParams& p, int k, bool replay, bool exact_pass, hipStream_t s);
 // Resident 256-thread workgroups per CU for the sweep kernel and the CU count.
 hipError_t round_sweep_occupancy(int k, bool replay, int* blocks_per_cu, int* cus);
-// Write back the V planes of stale tiles (p.vstale, p.pref_prev, p.round = the
-// round after the one that left them stale); k = 8 only.
-hipError_t launch_vv_materialize(const RoundParams& p, hipStream_t s);
-// Apply the pending +8 steps of deferred count planes (p.kpend) and clear them.
-hipError_t launch_kl_materialize(const RoundParams& p, hipStream_t s);
-// Both write-backs in one pass over runs of 16 tiles per wave (do_v: launch_vv_materialize's part,
-// do_k: launch_kl_materialize's); tiles with nothing deferred are skipped with no memory access.
+// k_materialize: both write-backs in one pass over runs of p.mat_run tiles per wave; tiles with
+// nothing deferred are skipped with no memory access. k = 8 only.
+// do_v: the V planes of stale tiles (p.vstale, p.pref_prev, p.round = the round after the one that
+// left them stale); do_k: the pending +8 steps of deferred count planes (p.kpend), then cleared.
 hipError_t launch_materialize(const RoundParams& p, bool do_v, bool do_k, hipStream_t s);
 
 // Need-masked exchange: the rows each rank's nodes draw in the rounds of one window.

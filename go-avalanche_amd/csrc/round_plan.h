@@ -1,0 +1,213 @@
+// Host-side round planning: what the engine knows about its records (RecordFacts), the decision a
+// round derives from it (plan_round) and the sweep grid's arithmetic (sweep_grid). Pure C++17, no HIP
+// include: host/round_plan_test.cpp checks it without a GPU. A round that plans klazy, vv or fresh on
+// a wrong fact corrupts records silently, so every fact changes only through the transitions below.
+#pragma once
+
+#include <algorithm>
+#include <cstdint>
+
+namespace avk {
+
+enum class RoundKernel : int {
+  Sweep,     // k_round_sweep (uncapped, k <= 8)
+  Node,      // k_round_node (capped, k <= 8)
+  FirstGen,  // k_round_fast / k_round_capped (any k; responder variants, non-polling nodes, A/B)
+};
+
+// The sweep kernel's build, as far as the records decide it. The launcher (round_sweep.hip
+// launch_sweep_k) adds what depends on the grid alone: Warm runs as the walking kModeWarm or, on a
+// resident grid smaller than the tile count, as kModeWarmPipe.
+enum class SweepMode : int { Replay, Ablate, Fresh, Warm, Check };
+
+struct PlanShape {
+  int k;
+  uint32_t BL;
+  int64_t N;
+  uint32_t NL, PS;
+  bool capped;
+  int peer_world;
+  bool has_comm;  // an RCCL communicator exchanges the rows
+  int32_t pub_mode;
+  bool any_nopoll;
+};
+
+// the options the decision reads (av_set_option)
+struct PlanKnobs {
+  int kernel;
+  bool virtual_votes;
+  uint32_t vv_min_bl;
+  bool count_lazy, k_hi_virtual, ref_rows, uni_rows, ablate_gather, unsynced_shard;
+};
+
+struct RoundPlan {
+  // responder variant 2 or non-polling nodes on a capped engine: no kernel runs them
+  bool unsupported;
+  RoundKernel kernel;
+  SweepMode mode;  // kernel == Sweep
+  int k;
+  bool replay, capped;
+  bool fresh;       // planes known to be zero are not read (kernels.h fresh)
+  bool warm;        // every consider plane all-ones: the sweep's warm sim modes
+  bool vv;          // vote planes left unstored (kernels.h vv)
+  bool vv_uniform;  // below vv_min_bl only the uniform form (a settled tile's V = A: nothing to regather)
+  bool klazy;       // count planes deferred (kernels.h klazy)
+  bool kconsume;    // the first warm round that can finalize applies the pending steps itself
+  bool hivirt;      // kernels.h kHiVirt
+  bool exact_pass;  // capped: a count may have reached 120
+  // deferred state the round cannot read through, written back before the launch
+  bool wb_votes, wb_counts;
+  // reference rows / uniform rows may be used; the caller clears these when no honest reference
+  // node exists (ref_pick reads the device)
+  bool ref_rows, uni_rows;
+};
+
+struct RecordFacts {
+  // every consider bit ever shifted in was 1 (no replay, no neutral drop-in
+  // vote, no write_records): an all-ones oldest consider plane implies all
+  // consider planes are all-ones (lets k_round_fast skip them)
+  bool c_monotone = true;
+  // every consider plane of every lane is all-ones: set after a sim round with k >= 8 in which every
+  // live record was polled (all targets valid, uncapped); cleared by anything that can write a 0
+  // consider bit (init, add, write_records, drop-in votes, replay)
+  bool warm_all = false;
+  // every record is a NewVoteRecord from av_init_records (votes = consider =
+  // count = 0): the next sweep round reads only the A plane (kernels.h fresh)
+  bool fresh = false;
+  // upper bound on any live record's count (confidence >> 1) at the start of the next round: a
+  // round adds at most k, init/add start at 0, anything else sets it to 127. While it is < 120 no
+  // record can finalize in the next round (k <= 8), so the capped path skips its exact pass.
+  int count_bound = 127;
+  bool v_stale = false;  // some tile may be stale
+  bool k_pend = false;   // some tile may hold pending steps or flags
+  // rflag_ok[b]: the reference-row flags of snapshot buffer b were written by the round that wrote
+  // its rows, against ref_node's row of the buffer that round read, and nothing has written either
+  // buffer since
+  bool rflag_ok[3] = {false, false, false};
+  // uni_ok[b]: buffer b was written by a sweep round that tagged its uniform-row slots
+  bool uni_ok[3] = {false, false, false};
+
+  // Anything but a reference-row sweep round that writes a snapshot buffer
+  // (drop-in votes, adds, writes, init, validity/publish-rule refreshes, peer
+  // and RCCL set-up, other round kernels) leaves its flags stale.
+  void snapshot_written() {
+    rflag_ok[0] = rflag_ok[1] = rflag_ok[2] = false;
+    uni_ok[0] = uni_ok[1] = uni_ok[2] = false;
+  }
+  // av_init_records: every plane is rewritten (the caller clears the tile words of what was deferred).
+  // Every record starts at count 0 with no considered vote (NewVoteRecord, vote.go:33-35), and a
+  // count step needs > 6 considered votes in the 8-vote window (vote.go:58-61): the first 6 votes
+  // of a fresh record cannot step it, so after v votes every count is <= v - 6
+  void init(bool records_created) {
+    snapshot_written();
+    warm_all = false;
+    count_bound = -6;
+    v_stale = k_pend = false;
+    fresh = records_created;
+  }
+  void add_targets() {
+    warm_all = false;
+    fresh = false;
+  }
+  // drop-in votes: at most one confidence step per vote, so the most votes one node gets bound the
+  // counts; a neutral vote shifts in consider = 0
+  void dropin_votes(int64_t max_node_votes, bool any_neutral) {
+    fresh = false;
+    count_bound = (int)std::min<int64_t>(127, count_bound + max_node_votes);
+    if (any_neutral) c_monotone = false;
+  }
+  void write_records() {
+    c_monotone = false;
+    fresh = false;
+    count_bound = 127;  // arbitrary counts written
+  }
+  void replay_call() { c_monotone = false; }  // replayed votes may be neutral
+  void votes_written_back() { v_stale = false; }
+  void counts_written_back() { k_pend = false; }
+  // the responders' re-adds (pub_mode 2) create records after the round's votes
+  void responder_readds() {
+    warm_all = false;
+    count_bound = 127;
+  }
+  void option_fresh_off() { fresh = false; }          // option "fresh" = 0
+  void option_warm_skip_off() { c_monotone = false; }  // option "warm_skip" = 0: may only be switched off
+  // A round ran by `p` and published snapshot buffer out_buf. all_valid: every target of the shard is
+  // valid; refw: the launch wrote reference-row flags for the snapshot it published.
+  void after_round(const RoundPlan& p, bool all_valid, bool refw, int out_buf) {
+    if (p.vv) v_stale = true;
+    if (p.klazy) k_pend = true;
+    if (p.kconsume) k_pend = false;
+    if (p.fresh && p.hivirt) k_pend = true;  // the fresh round flags its tiles kHiVirt
+    count_bound = std::min(127, count_bound + p.k);
+    fresh = false;
+    rflag_ok[out_buf] = p.ref_rows && refw;
+    uni_ok[out_buf] = p.uni_rows;
+    if (p.replay)
+      warm_all = false;
+    else if (c_monotone && p.k >= 8 && !p.capped && all_valid)
+      warm_all = true;  // every live record was polled and shifted in 8 considered votes
+  }
+};
+
+// The whole per-round decision, a pure function of its arguments.
+inline RoundPlan plan_round(const RecordFacts& f, const PlanShape& s, const PlanKnobs& o, bool replay) {
+  RoundPlan r{};
+  r.k = s.k;
+  r.replay = replay;
+  r.capped = s.capped;
+  // responder variants and non-polling nodes run the first-generation kernels
+  const bool compat = s.pub_mode != 0 || s.any_nopoll;
+  r.unsupported = compat && s.capped && (s.pub_mode == 2 || s.any_nopoll);
+  // the sweep addresses the preference table by 32-bit byte offsets
+  const bool sweep = o.kernel == 2 && s.k <= 8 && !s.capped && !compat && (uint64_t)s.N * s.PS < (1ull << 30);
+  r.kernel = sweep                                             ? RoundKernel::Sweep
+             : o.kernel == 2 && s.k <= 8 && s.capped && !compat ? RoundKernel::Node
+                                                                : RoundKernel::FirstGen;
+  const bool ones = f.c_monotone && f.warm_all;
+  // the round after av_init_records: planes known to be zero are not read
+  r.fresh = f.fresh && sweep && !replay && !o.ablate_gather;
+  r.warm = sweep && !replay && ones && !o.ablate_gather && !r.fresh;
+  r.mode = replay            ? SweepMode::Replay
+           : o.ablate_gather ? SweepMode::Ablate
+           : r.fresh         ? SweepMode::Fresh
+           : ones            ? SweepMode::Warm
+                             : SweepMode::Check;
+  // vote planes may be left unstored: warm (or fresh) k = 8 sim rounds
+  r.vv = o.virtual_votes && s.k == 8 && (r.warm || r.fresh);
+  r.vv_uniform = r.vv && s.BL < o.vv_min_bl;
+  // count planes may be deferred: warm k = 8 sim rounds while no record can
+  // finalize (every true count < 120 at round start)
+  r.klazy = o.count_lazy && r.warm && s.k == 8 && f.count_bound < 120;
+  r.kconsume = !r.klazy && f.k_pend && r.warm && s.k == 8;
+  r.hivirt = o.k_hi_virtual && s.k == 8;
+  r.exact_pass = f.count_bound >= 120;
+  r.wb_votes = !r.vv && f.v_stale;
+  r.wb_counts = !r.klazy && !r.kconsume && f.k_pend;
+  // reference rows: sweep rounds at k = 8 with a node's lanes inside one wave
+  const bool tagged = sweep && s.k == 8 && !replay && !s.has_comm && !o.ablate_gather;
+  r.ref_rows = o.ref_rows && tagged && 64 % s.BL == 0;
+  // uniform rows: a node-sharded engine sees every row only through the peer exchange, whose pushes
+  // carry the slots (unsynced_shard, diagnostics: a rank's share alone, on its own slot)
+  r.uni_rows = o.uni_rows && tagged && (s.NL == (uint32_t)s.N || s.peer_world > 1 || o.unsynced_shard);
+  return r;
+}
+
+// The sweep grid over `tiles` 64-lane tiles: `blocks` resident workgroups of 4 waves (0 = one wave
+// per tile), never more than the tiles need; each wave owns a run of `run` consecutive tiles (or, for
+// runs the kernel does not take, walks the same number with the grid's stride).
+struct SweepGrid {
+  uint32_t grid, run;
+};
+inline SweepGrid sweep_grid(uint32_t tiles, uint32_t blocks) {
+  const uint32_t need = (uint32_t)(((uint64_t)tiles + 3u) / 4u);
+  const uint32_t grid = std::max(1u, blocks ? std::min(blocks, need) : need);
+  const uint64_t waves = (uint64_t)grid * 4u;
+  return {grid, (uint32_t)((tiles + waves - 1u) / waves)};
+}
+// waves of that grid that own a run (the fewest that write the StatusUpdate log)
+inline uint64_t sweep_run_waves(uint32_t tiles, uint32_t blocks) {
+  const uint64_t run = std::max(1u, sweep_grid(tiles, blocks).run);
+  return std::max<uint64_t>(1, (tiles + run - 1u) / run);
+}
+
+}  // namespace avk

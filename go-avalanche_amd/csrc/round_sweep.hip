@@ -34,6 +34,7 @@
 
 #include "kernels.h"
 #include "round_common.h"
+#include "round_plan.h"
 #include "round_slots.h"
 
 // A/B build knob: the StatusUpdate log reservation issued before the tile's stores (1) or after
@@ -1158,20 +1159,20 @@ __device__ __forceinline__ uint32_t settled_run_uni(const RoundParams& p, uint32
 // Everything else that writes kpend, a record plane, the validity words or a snapshot row, and why
 // no tile is taken as quiescent afterwards while its row of pref_out or its A differs from what
 // the walk would publish. Two guards: a write-back clears pend (k_materialize, launched by
-// materialize_votes / materialize_counts in engine.cpp, zeroes every kpend word), so two deferred
-// rounds must follow it; ref_invalidate drops uni_ok of all three buffers, so `uniform` is false in
+// materialize in engine.cpp, zeroes every kpend word), so two deferred
+// rounds must follow it; facts.snapshot_written drops uni_ok of all three buffers, so `uniform` is false in
 // the next round and prev_uni in the next two.
 //  * av_register_votes(_batch), av_add_targets, av_write_records: materialize_votes first (pend = 0,
-//    kPendAllLive gone) and ref_invalidate; they republish the rows they change into the current
+//    kPendAllLive gone) and facts.snapshot_written; they republish the rows they change into the current
 //    snapshot (k_register_votes, k_add_targets, refresh_pref), which is pref_out three rounds later:
 //    (3) holds with "the call that rewrote the records".
-//  * av_set_valid: materialize_votes (pend = 0) and ref_invalidate; A and the rows are untouched, and
+//  * av_set_valid: materialize_votes (pend = 0) and facts.snapshot_written; A and the rows are untouched, and
 //    the new polled set is first seen by the general path (kPendAllLive cleared).
-//  * av_init_records: kpend zeroed, ref_invalidate, every plane and the current snapshot rewritten;
+//  * av_init_records: kpend zeroed, facts.snapshot_written, every plane and the current snapshot rewritten;
 //    the fresh round after it defers nothing (klazy needs a warm round).
 //  * av_materialize and every other write-back: pend = 0. av_read_records, av_census, av_read_pref
 //    read through the deferred forms and write nothing.
-//  * av_set_option (every option, this one too): ref_invalidate; count_lazy and k_hi_virtual write
+//  * av_set_option (every option, this one too): facts.snapshot_written; count_lazy and k_hi_virtual write
 //    back first; responder republishes and leaves the sweep.
 //  * the replay, capped and first-generation round kernels, and a sweep round that is not klazy:
 //    launch_one_round / launch_replay_fused write the counts back first (pend = 0) and leave
@@ -1519,128 +1520,40 @@ hipError_t launch_mode(const RoundParams& p, uint32_t grid, hipStream_t s) {
   return launch_mode_cc<K, MODE, true>(p, grid, s);
 }
 
+// mode: the round plan's (round_plan.h); what depends on the grid alone is decided here.
 template <int K>
-hipError_t launch_sweep_k(const RoundParams& p_in, bool replay, uint32_t blocks, hipStream_t s, bool* ref_written) {
+hipError_t launch_sweep_k(const RoundParams& p_in, SweepMode mode, uint32_t blocks, hipStream_t s, bool* ref_written) {
   if (ref_written) *ref_written = false;
-  const uint32_t need = (p_in.Lpad / 64u + 3u) / 4u;
-  const uint32_t grid = std::max(1u, blocks ? std::min(blocks, need) : need);
+  const uint32_t tiles = p_in.Lpad / 64u;
+  const SweepGrid g = sweep_grid(tiles, blocks);
   RoundParams p = p_in;
   p.tpw = 0u;
   // deferred pushes: every wave of the grid takes at most kPushQ tiles (a run, or a grid stride over
   // <= kPushQ tiles) and at most 8 peers (the queue's byte per lane); the resident pipelined grid and
   // larger worlds push from the tile loop
-  {
-    const uint32_t waves = grid * 4u, tiles = p.Lpad / 64u;
-    p.push_q = p.push_defer && p.push_n && p.push_n <= 8u && (tiles + waves - 1u) / waves <= kPushQ ? 1u : 0u;
-  }
-  if (p_in.tpw && K == 8 && !replay && !p.ablate_gather && !p.fresh && p.warm_skip && p.warm_all) {
-    // p_in.tpw = enabled: each wave takes a run of consecutive tiles
-    const uint32_t tiles = p.Lpad / 64u, waves = grid * 4u;
-    p.tpw = (tiles + waves - 1u) / waves;
-    if (p.tpw > 16u) p.tpw = 0u;  // long runs: grid stride (their nodes overflow the shared draw anyway)
-    if (p.tpw) {
-      if (ref_written) *ref_written = p.rflag_out != nullptr;
-      return launch_mode<K, kModeWarm>(p, grid, s);
-    }
+  p.push_q = p.push_defer && p.push_n && p.push_n <= 8u && g.run <= kPushQ ? 1u : 0u;
+  // p_in.tpw = enabled: each wave takes a run of consecutive tiles
+  // (long runs: grid stride; their nodes overflow the shared draw anyway)
+  if (mode == SweepMode::Warm && p_in.tpw && K == 8 && g.run && g.run <= 16u) {
+    p.tpw = g.run;
+    if (ref_written) *ref_written = p.rflag_out != nullptr;
+    return launch_mode<K, kModeWarm>(p, g.grid, s);
   }
   p.rflag_out = nullptr;  // only the walking warm mode writes reference-row flags
   p.rflag_in = nullptr;
-  if (replay) return launch_mode<K, kModeReplay>(p, grid, s);
-  if (p.ablate_gather) return launch_mode<K, kModeAblate>(p, grid, s);
-  if (p.fresh) return launch_mode<K, kModeFresh>(p, grid, s);
-  if (p.warm_skip && p.warm_all) {  // a resident grid walks several tiles per wave: pipeline them
-    if (blocks && grid < need && !p.nopipe) {
-      p.push_q = 0u;
-      return launch_mode<K, kModeWarmPipe>(p, grid, s);
-    }
-    return launch_mode<K, kModeWarm>(p, grid, s);
+  switch (mode) {
+    case SweepMode::Replay: return launch_mode<K, kModeReplay>(p, g.grid, s);
+    case SweepMode::Ablate: return launch_mode<K, kModeAblate>(p, g.grid, s);
+    case SweepMode::Fresh: return launch_mode<K, kModeFresh>(p, g.grid, s);
+    case SweepMode::Warm:  // a resident grid walks several tiles per wave: pipeline them
+      if (blocks && g.grid < (tiles + 3u) / 4u && !p.nopipe) {
+        p.push_q = 0u;
+        return launch_mode<K, kModeWarmPipe>(p, g.grid, s);
+      }
+      return launch_mode<K, kModeWarm>(p, g.grid, s);
+    case SweepMode::Check: break;
   }
-  return launch_mode<K, kModeCheck>(p, grid, s);
-}
-
-// Materialize stale V planes (kernels.h vv) before anything other than a warm
-// k = 8 sim round reads or writes the records: the vote register of a stale
-// tile is the last round's 8 gathered votes, V_i = slot 7 - i.
-__global__ __launch_bounds__(256) void k_vv_materialize(const RoundParams p) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t tile = uni(blockIdx.x * 4u + (threadIdx.x >> 6));
-  const uint32_t raw = tile < (p.Lpad >> 6) ? uni(p.vstale[tile]) : 0u;
-  if (raw == 0u) return;
-  const uint32_t st = raw & kVMask;
-  const LaneIdx x = lane_idx(p, tile, lane);
-  if (raw & kCAll) {  // consider planes: all-ones
-    if (x.active) {
-      uint32_t* const tp = p.planes + (size_t)tile * (kPlanes * 64u);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) tp[1024u + (uint32_t)i * 64u + lane] = ~0u;
-    }
-    if (st == 0u) {
-      if (lane == 0) p.vstale[tile] = 0u;
-      return;
-    }
-  }
-  u32x4 o0, o1;
-  if (st == kVUniform) {  // V_i = A on every polled record
-    const uint32_t A = p.planes[(size_t)tile * (kPlanes * 64u) + 1536u + lane];
-    o0 = o1 = u32x4{A, A, A, A};
-  } else {
-    const uint32_t nlA = uni(x.nl), nn = (uint32_t)__builtin_amdgcn_readlane((int)x.nl, 63) - nlA + 1u;
-    uint32_t pp[8];
-    draw_peers<8>(p, p.round - 1u, x.node, x.nl, nlA, nn, lane, pp);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      o0[i] = p.pref_prev[pp[7 - i] * p.PS + x.b];
-      o1[i] = p.pref_prev[pp[3 - i] * p.PS + x.b];
-    }
-  }
-  if (x.active) {
-    u32x4* const grp = reinterpret_cast<u32x4*>(p.planes + (size_t)tile * (kPlanes * 64u)) + lane;
-    grp[0] = o0;
-    grp[64] = o1;
-  }
-  if (lane == 0) p.vstale[tile] = 0u;
-}
-
-// Apply deferred count planes (kernels.h klazy): + 8 * pending on the polled
-// (live, valid) records of each tile with pending steps, then clear them.
-__global__ __launch_bounds__(256) void k_kl_materialize(const RoundParams p) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t tile = uni(blockIdx.x * 4u + (threadIdx.x >> 6));
-  if (tile >= (p.Lpad >> 6)) return;
-  const uint32_t kw = uni(p.kpend[tile]);
-  const uint32_t pend = kw & 0xFFu;
-  if (kw == 0u) return;
-  const LaneIdx x = lane_idx(p, tile, lane);
-  if ((pend || (kw & kHiVirt)) && x.active) {
-    u32x4* const grp = reinterpret_cast<u32x4*>(p.planes + (size_t)tile * (kPlanes * 64u)) + lane;
-    const u32x4 k0 = grp[128];
-    const u32x4 k1 = kw & kHiVirt ? u32x4{0u, 0u, 0u, ~real_mask(p.tn, x.b)} : grp[192];  // kernels.h kHiVirt
-    uint32_t Kp[8];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      Kp[i] = k0[i];
-      Kp[4 + i] = k1[i];
-    }
-    const uint32_t P0 = ~Kp[7] & p.valid[x.b];
-    uint32_t cy = 0u;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {  // + pend on count bits 3..6
-      const uint32_t bi = ((pend >> i) & 1u) ? P0 : 0u;
-      const uint32_t t = Kp[3 + i] ^ bi;
-      const uint32_t si = t ^ cy;
-      cy = (t & cy) | (Kp[3 + i] & bi);
-      Kp[3 + i] = si;
-    }
-    u32x4 o0, o1;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      o0[i] = Kp[i];
-      o1[i] = Kp[4 + i];
-    }
-    grp[128] = o0;
-    grp[192] = o1;
-  }
-  if (lane == 0) p.kpend[tile] = 0u;
+  return launch_mode<K, kModeCheck>(p, g.grid, s);
 }
 
 // The write-back's stores non-temporal (a write-only stream; the next round streams the planes back
@@ -1650,8 +1563,10 @@ __global__ __launch_bounds__(256) void k_kl_materialize(const RoundParams p) {
 #ifndef AVK_MAT_NT
 #define AVK_MAT_NT 1
 #endif
-// Both deferred forms written back in one pass (do_v: stale vote planes and unstored consider planes,
-// as k_vv_materialize; do_k: pending count steps and virtual K4..K7 groups, as k_kl_materialize).
+// k_materialize writes back both deferred forms in one pass, before anything other than a warm k = 8
+// sim round reads or writes the records (do_v: stale vote planes, whose vote register is the last
+// round's 8 gathered votes, V_i = slot 7 - i, and unstored consider planes; do_k: pending count steps
+// (kernels.h klazy: + 8 * pending on the polled records) and virtual K4..K7 groups).
 // Per tile every load (A for a uniform vote register, the K groups, a stale tile's peer rows) is issued
 // before any store: vmcnt counts loads and stores in issue order, so a load issued after the tile's
 // consider-plane stores waited for their write acknowledgements too (round 5's walking version paid
@@ -1779,18 +1694,11 @@ hipError_t occupancy_k(bool replay, int* bpc) {
     default: return hipErrorInvalidValue; \
   }
 
-hipError_t launch_round_sweep(const RoundParams& p, int k, bool replay, uint32_t blocks, hipStream_t s,
+hipError_t launch_round_sweep(const RoundParams& p, int k, SweepMode mode, uint32_t blocks, hipStream_t s,
                               bool* ref_written) {
-#define AVK_SW(K) launch_sweep_k<K>(p, replay, blocks, s, ref_written)
+#define AVK_SW(K) launch_sweep_k<K>(p, mode, blocks, s, ref_written)
   AVK_SWEEP_SWITCH(k, AVK_SW)
 #undef AVK_SW
-}
-
-hipError_t launch_vv_materialize(const RoundParams& p, hipStream_t s) {
-  if (!p.vstale || !p.pref_prev) return hipErrorInvalidValue;
-  const uint32_t tiles = p.Lpad / 64u;
-  hipLaunchKernelGGL(k_vv_materialize, dim3((tiles + 3u) / 4u), dim3(256), 0, s, p);
-  return hipGetLastError();
 }
 
 hipError_t launch_materialize(const RoundParams& p, bool do_v, bool do_k, hipStream_t s) {
@@ -1800,13 +1708,6 @@ hipError_t launch_materialize(const RoundParams& p, bool do_v, bool do_k, hipStr
   const uint32_t tiles = p.Lpad / 64u;
   const uint32_t waves = (tiles + run - 1u) / run;
   hipLaunchKernelGGL(k_materialize, dim3((waves + 3u) / 4u), dim3(256), 0, s, p, run, do_v ? 1u : 0u, do_k ? 1u : 0u);
-  return hipGetLastError();
-}
-
-hipError_t launch_kl_materialize(const RoundParams& p, hipStream_t s) {
-  if (!p.kpend) return hipErrorInvalidValue;
-  const uint32_t tiles = p.Lpad / 64u;
-  hipLaunchKernelGGL(k_kl_materialize, dim3((tiles + 3u) / 4u), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 

@@ -415,7 +415,12 @@ int av_sample_peers(av_engine* e, int64_t round, int64_t n0, int64_t n1, int32_t
  * uniform input snapshots takes its count step with no A-plane read and no
  * republished row; engines without an exchange; exact),
  * "wave_dense" (0; n: a wave with >= n lanes holding updates logs them all as
- * dense records; exact, measured slower).
+ * dense records; exact, measured slower), "uniform_rows" (1: uniform-row
+ * settled tests), "k_hi_virtual" (1: the K4..K7 count planes left unstored
+ * while every count is < 16), "settled_lean" (1), "replay_fast" (1),
+ * "dropin_fast" (1; 0: drop-in batches always take the sort-grouped path),
+ * "push_store" (1: plain peer stores; 0: system scope; 2: none, results
+ * invalid), "census_blocks" (0: av_census's grid by size).
  * StatusUpdate delivery: "enc_buckets" (2^26: (round, node) buckets per
  * encoder pass; a log spanning more takes several passes), "copy_blocks" (0:
  * the compact stream's copy to host memory by the runtime's copy; n: by an
@@ -423,7 +428,8 @@ int av_sample_peers(av_engine* e, int64_t round, int64_t n0, int64_t n1, int32_t
  * Diagnostics that make results invalid: "ablate_gather",
  * "ablate_emit" (StatusUpdates counted, not stored), "ablate_node"
  * (k_round_node: 1 = lanes past the cap skipped, 4 = no plane stores),
- * "unsynced_shard". Diagnostics that leave results valid: "count_changed"
+ * "unsynced_shard", "ablate_phase". Diagnostics that leave results valid:
+ * "round_marker" (1: a timing-free event after every round), "count_changed"
  * (1: count changed published words in every sweep round, av_changed_words),
  * "solo_barrier" (1: a one-rank peer barrier after every round of an engine
  * without an exchange: the barrier's fixed cost alone), "warm_pref" (1: the

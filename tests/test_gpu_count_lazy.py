@@ -2,7 +2,7 @@
 round in which no record can finalize, a tile whose polled records all agreed
 with their accepted bit on all 8 votes gains exactly +8 on every polled count
 (vote.go:66-69); it leaves its K planes unstored and counts the pending steps
-per tile. Any other access first applies them (k_kl_materialize). These tests
+per tile. Any other access first applies them (k_materialize). These tests
 run honest networks (where tiles defer) with reads, validity flips, drop-in
 votes and option switches interleaved, and compare with the oracle bit for
 bit; and the same network with the option on and off."""

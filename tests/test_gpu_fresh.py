@@ -67,7 +67,7 @@ def test_fresh_virtual_consider_writeback(oracle, path):
     """The fresh round leaves the consider planes of its tiles unstored
     (kernels.h kCAll: all-ones after 8 sim votes). Every operation that reads
     or writes the planes right after it must see them as all-ones (write-back
-    in k_vv_materialize; k_read_records_v reads them virtually); the rounds
+    in k_materialize; k_read_records_v reads them virtually); the rounds
     after it must match the oracle bit for bit."""
     n, m, k, seed = 300, 1000, 8, 29
     eng = avhip.Engine(n, m, k=k, seed=seed, log_capacity=1 << 22)

@@ -2,7 +2,7 @@
 sim round a tile may leave its vote planes unstored, because a record's vote
 register after 8 sim votes is exactly that round's 8 gathered votes
 (vote.go:55). The next round regathers them from the previous snapshot; any
-other access first writes them back (k_vv_materialize). These tests run long
+other access first writes them back (k_materialize). These tests run long
 stretches of rounds with no state read in between (stale tiles carried from
 round to round), interleave every operation that must write the planes back,
 and compare with the oracle bit for bit."""

@@ -3,7 +3,7 @@
 round-kernel time (HIP events), applied votes and StatusUpdates. Run it under
 rocprofv3 (--kernel-trace / --pmc) to attribute counters to rounds: after the
 init kernels, the i-th round-kernel dispatch is round i (write-back passes
-named k_kl_materialize / k_vv_materialize sit between them).
+named k_materialize sit between them).
 
     python tools/round_probe.py --workload c4 --rounds 16 [--option name=value ...] [--json out.json]
 """
