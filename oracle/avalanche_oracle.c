@@ -418,6 +418,28 @@ int avo_sim_register_votes(avo_sim* s, int64_t node, const int64_t* targets, con
   return r;
 }
 
+/* The engine's av_write_records over nodes [n0, n1) x targets [t0, t1): a word
+ * with count >= 128 leaves no record and sets the remembered decision from
+ * bit 16; any other word becomes the record itself. The published preference
+ * follows as in avo_sim_add. */
+void avo_sim_write_records(avo_sim* s, int64_t n0, int64_t n1, int64_t t0, int64_t t1, const uint32_t* words) {
+  const int64_t m = s->cfg.n_targets, w = t1 - t0;
+  for (int64_t j = n0; j < n1; ++j) {
+    avo_processor* p = s->procs[j];
+    for (int64_t t = t0; t < t1; ++t) {
+      const uint32_t word = words[(j - n0) * w + (t - t0)];
+      if ((word >> 17) >= AVO_FINALIZATION_SCORE) {
+        p->present[t] = 0;
+        p->decision[t] = (uint8_t)((word >> 16) & 1u);
+      } else {
+        p->present[t] = 1;
+        p->rec[t] = avo_unpack(word);
+      }
+      s->pref[j * m + t] = (uint8_t)published_pref_mode(p, t, s->responder);
+    }
+  }
+}
+
 typedef struct {
   int64_t* rows; /* 5 columns */
   int64_t n, cap;

@@ -168,6 +168,9 @@ int avo_sim_is_byzantine(const avo_sim* s, int64_t node);
 int avo_sim_add(avo_sim* s, int64_t node, int64_t t, int accepted);
 int avo_sim_register_votes(avo_sim* s, int64_t node, const int64_t* targets, const uint32_t* errs,
                            int64_t n, int64_t* out_targets, int32_t* out_status, int64_t* n_out);
+/* Canonical record words written over nodes [n0, n1) x targets [t0, t1) (the engine's
+ * av_write_records): count >= 128 = no record, decision from bit 16; else avo_unpack(word). */
+void avo_sim_write_records(avo_sim* s, int64_t n0, int64_t n1, int64_t t0, int64_t t1, const uint32_t* words);
 
 /* ---- synthetic workload definition (same formulas as the device side) ---- */
 void avo_sample_peers(uint64_t seed, int64_t node, int64_t round, int64_t n_nodes, int32_t k,

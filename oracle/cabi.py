@@ -89,6 +89,8 @@ def lib():
         L.avo_sim_add.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int]
         L.avo_sim_register_votes.argtypes = [C.c_void_p, C.c_int64, i64p, u32p, C.c_int64, i64p, i32p,
                                              C.POINTER(C.c_int64)]
+        L.avo_sim_write_records.restype = None
+        L.avo_sim_write_records.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, u32p]
         L.avo_sample_peers.argtypes = [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, i64p]
         L.avo_is_byzantine.argtypes = [C.c_uint64, C.c_int64, C.c_uint32]
         L.avo_initial_accept.argtypes = [C.c_uint64, C.c_int32, C.c_uint32, C.c_int64, C.c_int64]
@@ -223,6 +225,13 @@ class Sim:
         n = C.c_int64(0)
         lib().avo_sim_register_votes(self._h, node, targets, errs, len(targets), ot, os_, C.byref(n))
         return list(zip(ot[: n.value].tolist(), os_[: n.value].tolist()))
+
+    def write_records(self, words, n0=0, t0=0):
+        """The engine's av_write_records: canonical words over nodes n0.. x targets t0..
+        (count >= 128: no record, decision from bit 16)."""
+        w = np.ascontiguousarray(words, np.uint32)
+        assert w.ndim == 2 and 0 <= n0 and n0 + w.shape[0] <= self.n and 0 <= t0 and t0 + w.shape[1] <= self.m
+        lib().avo_sim_write_records(self._h, n0, n0 + w.shape[0], t0, t0 + w.shape[1], w)
 
     def run_round(self, replay_errs=None, threads=1, collect=True, round_rel=0):
         """Returns (updates int64[n,5] (round,node,slot,target,status), applied_votes).

@@ -390,3 +390,67 @@ def test_example_c1_oracle():
     sim, rounds, finalized, _ = run_example_oracle(cabi)
     assert (finalized >= 100).all()  # "Nodes fully finalized: 100"
     assert rounds == 134  # every record finalizes at its 134th vote (vote.go:66-69), one vote per round
+
+
+# ---------------------------------------------------------------- Sim.write_records
+def _written_words(rng, n, m):
+    cons = rng.integers(0, 256, size=(n, m)).astype(np.uint32)
+    votes = rng.integers(0, 256, size=(n, m)).astype(np.uint32) & cons
+    count = rng.integers(0, 128, size=(n, m)).astype(np.uint32)
+    count[rng.random((n, m)) < 0.3] = 127  # one agreeing conclusive vote away from finalizing
+    votes[count == 127] = np.where(rng.random(int((count == 127).sum())) < 0.5, 0xFF, 0)
+    cons[count == 127] = 0xFF
+    acc = rng.integers(0, 2, size=(n, m)).astype(np.uint32)
+    words = votes | (cons << 8) | (((count << 1) | acc) << 16)
+    gone = rng.random((n, m)) < 0.2  # count >= 128, some with stray low bits
+    words[gone] = ((rng.integers(128, 32768, int(gone.sum())).astype(np.uint32) << 17) | (acc[gone] << 16) |
+                   rng.integers(0, 1 << 16, int(gone.sum())).astype(np.uint32))
+    return words.astype(np.uint32)
+
+
+def test_sim_write_records(oracle):
+    """Sim.write_records (the engine's av_write_records): dump() returns the written words in
+    canonical form, the published preference follows, and the next round is transition_batch
+    applied per polled vote."""
+    n, m, k, seed = 3, 40, 2, 5
+    rng = np.random.default_rng(3)
+    sim = oracle.Sim(n, m, k, seed=seed, init_mode=0)
+    words = _written_words(rng, n, m)
+    sim.write_records(words)
+    live = (words >> 17) < 128
+    acc = ((words >> 16) & 1).astype(np.uint8)
+    canon = np.where(live, words, 0xFFFE0000 | (acc.astype(np.uint32) << 16)).astype(np.uint32)
+    assert live.any() and (~live).any()
+    assert np.array_equal(sim.dump(), canon)
+    assert np.array_equal(sim.pref(), acc)
+    # a sub-rectangle overwrites only itself
+    patch = _written_words(rng, 2, 7)
+    sim.write_records(patch, n0=1, t0=30)
+    words[1:3, 30:37] = patch
+    live = (words >> 17) < 128
+    acc = ((words >> 16) & 1).astype(np.uint8)
+    canon = np.where(live, words, 0xFFFE0000 | (acc.astype(np.uint32) << 16)).astype(np.uint32)
+    assert np.array_equal(sim.dump(), canon)
+    assert np.array_equal(sim.pref(), acc)
+    sim.set_valid(4, False)
+
+    exp_rows, state, applied = [], canon.copy(), 0
+    for node in range(n):
+        peers = oracle.sample_peers(seed, node, 0, n, k)
+        for slot in range(k):
+            for t in range(m):
+                w = state[node, t]
+                if (w >> 17) >= 128 or t == 4:
+                    continue
+                err = 0 if acc[peers[slot], t] else 1
+                out, changed, status = oracle.transition_batch(np.array([w], np.uint32), np.array([err], np.uint32))
+                applied += 1
+                w2 = int(out[0])
+                if changed[0]:
+                    exp_rows.append((0, node, slot, t, int(status[0])))
+                state[node, t] = w2 if (w2 >> 17) < 128 else 0xFFFE0000 | (w2 & 0x10000)
+    got, got_applied = sim.run_round()
+    assert [tuple(r) for r in got.tolist()] == exp_rows
+    assert any(r[4] in (0, 3) for r in exp_rows), "no written record finalized in the round"
+    assert got_applied == applied
+    assert np.array_equal(sim.dump(), state)
