@@ -261,6 +261,12 @@ struct av_engine {
   uint32_t wave_dense = 0;  // option "wave_dense" (kernels.h RoundParams::wave_dense; A/B)
   uint32_t uni_votes = 1;   // option "uni_votes" (kernels.h RoundParams::uni_votes)
   uint32_t quiet_tiles = 1; // option "quiet_tiles" (kernels.h RoundParams::quiet_tiles; 0: every settled tile is walked)
+  // network-quiet rounds (kernels.h nq_*): option "net_quiet" (0: every run tests its own tiles) and
+  // "net_quiet_group", the runs a leader wave takes (A/B on MI355X, profiles/r09/ab_net_quiet.log)
+  uint32_t net_quiet = 1;
+  uint32_t nq_group = 16;
+  uint32_t nq_front = 1;    // option "net_quiet_front" (kernels.h nq_front; 0: every nq_group-th wave leads, A/B)
+  uint32_t* nq = nullptr;   // [0], [1]: the word of even / odd rounds; [2]: rounds that took the path
   int32_t pub_mode = 0;
   uint32_t* readd = nullptr;     // [L] pub_mode 2: re-add marks
   uint32_t* died_out = nullptr;  // [L] pub_mode 2: records deleted this round
@@ -638,7 +644,8 @@ avk::RoundPlan plan_for(const av_engine* e, bool replay) {
   const avk::PlanShape shape{e->k,       e->BL,         e->N,           e->NL,       e->PS,
                              e->capped,  e->peer_world, e->comm != nullptr, e->pub_mode, e->any_nopoll};
   const avk::PlanKnobs knobs{e->kernel,       e->virtual_votes, e->vv_min_bl, e->count_lazy,    e->k_hi_virtual,
-                             e->ref_rows,     e->uni_rows,      e->ablate_gather, e->unsynced_shard};
+                             e->ref_rows,     e->uni_rows,      e->ablate_gather, e->unsynced_shard,
+                             e->quiet_tiles != 0, e->net_quiet != 0, e->count_changed};
   return avk::plan_round(e->facts, shape, knobs, replay);
 }
 
@@ -798,6 +805,13 @@ int launch_one_round(av_engine* e, const uint32_t* replay) {
   const int nb = av_engine::nxt(e->cur);
   fill_push_params(e, sweep && !replay, nb, p);
   AV_TRY(fill_row_params(e, plan, nb, p));
+  if (plan.net_quiet_out) {  // the network-quiet word: this round's, and the last round's if it holds
+    p.nq_out = e->nq + (e->round & 1);
+    p.nq_in = plan.net_quiet_in ? e->nq + ((e->round & 1) ^ 1) : nullptr;
+    p.nq_rounds = e->nq + 2;
+    p.nq_group = e->nq_group;
+    p.nq_front = e->nq_front;
+  }
   if (e->warm_pref && sweep) {  // diagnostics (untimed): the round's gather sources, read once
     if (!e->touch_sink) AV_HIP(hipMalloc(&e->touch_sink, 64));
     AV_HIP(avk::launch_touch(p.pref_prev, (size_t)e->N * e->PS * 4u, e->touch_sink, e->stream));
@@ -1052,7 +1066,7 @@ int av_destroy(av_engine* e) {
   void* bufs[] = {e->planes, e->pref[0], e->pref[1], e->pref[2], e->vstale, e->kpend, e->valid, e->byz, e->log, e->log_count, e->log_overflow, e->node_flags,
                   e->readd, e->died_out, e->nopoll,
                   e->dlog, e->upd_count, e->mlog,
-                  e->applied, e->bytes, e->finalized, e->scratch_count, e->replay,
+                  e->applied, e->bytes, e->finalized, e->scratch_count, e->replay, e->nq,
                   e->need_mine, e->needmask, e->stale, e->group ? e->needin : nullptr};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -1186,6 +1200,8 @@ int av_create(const av_config* cfg, av_engine** out) {
   if ((he = dev_alloc(&e->scratch_count, 1)) != hipSuccess) return hip_fail(he, "alloc counters");
   if ((he = dev_alloc(&e->changed, 3 * avk::kLogShards)) != hipSuccess) return hip_fail(he, "alloc counters");
   (void)hipMemsetAsync(e->changed, 0, 3 * avk::kLogShards * 8, e->stream);
+  if ((he = dev_alloc(&e->nq, 4)) != hipSuccess) return hip_fail(he, "alloc counters");
+  (void)hipMemsetAsync(e->nq, 0, 4 * 4, e->stream);
 
   (void)hipMemsetAsync(e->log_overflow, 0, 4, e->stream);
   (void)hipMemsetAsync(e->applied, 0, avk::kLogShards * 8, e->stream);
@@ -2465,6 +2481,17 @@ int av_changed_words(av_engine* e, int64_t* words, int64_t* segments) {
   return sum_counter(e, e->changed + avk::kLogShards, segments);
 }
 
+int av_net_quiet_rounds(av_engine* e, int64_t* out) {
+  AV_ENTER(e);
+  AV_PEER_SYNC_CHECK(e);
+  AV_CHECK(out, AV_ERR_INVALID_ARG, "null argument");
+  uint32_t v = 0;
+  AV_HIP(hipMemcpyAsync(&v, e->nq + 2, 4, hipMemcpyDeviceToHost, e->stream));
+  AV_HIP(hipStreamSynchronize(e->stream));
+  *out = (int64_t)v;
+  return AV_OK;
+}
+
 int av_materialize(av_engine* e) {
   AV_ENTER(e);
   AV_PEER_CHECK(e);
@@ -2560,6 +2587,9 @@ constexpr PlainOption kPlainOptions[] = {
     opt("uni_merge", &av_engine::uni_merge, kReject, 1, 16),  // runs per wave, uniform-input rounds
     opt("uni_votes", &av_engine::uni_votes),            // uniform input: the reference word as every tile's votes
     opt("quiet_tiles", &av_engine::quiet_tiles),        // A/B: quiescent settled tiles skip the A read and the republish
+    opt("net_quiet", &av_engine::net_quiet),            // A/B: rounds after a fully quiescent round skip the per-run work
+    opt("net_quiet_group", &av_engine::nq_group, kReject, 1, 16),  // runs per leader wave of such a round
+    opt("net_quiet_front", &av_engine::nq_front),       // A/B: 0 = every net_quiet_group-th wave leads, not the grid's first
     opt("wave_dense", &av_engine::wave_dense, kReject, 0, 64),  // A/B: dense records per wave (0 off)
     opt("tile_draw", &av_engine::tile_draw, kReject, 0, 1),  // A/B: per-tile shared draws in overflowing runs
     opt("materialize_run", &av_engine::mat_run, kReject, 1, 64),  // A/B: tiles per wave of the write-back

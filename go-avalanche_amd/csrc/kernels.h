@@ -247,6 +247,19 @@ struct RoundParams {
   uint32_t quiet_tiles;  // k = 8 warm sweep, single-engine build (option "quiet_tiles", default 1): a settled tile
                          // with two deferred rounds behind it and uniform input snapshots takes its +8 step with
                          // no A-plane read and no republished row (round_sweep.hip "Quiescent tiles")
+  // Network-quiet rounds (k = 8 warm sweep, single-engine build, klazy rounds with quiet_tiles; option
+  // "net_quiet", default 1; round_sweep.hip "Network-quiet rounds"). Two device words, used by round
+  // parity. nq_out: this round's word; a wave that owns tiles and whose run is not quiescent throughout
+  // stores p.round + 1 into it, a fully quiescent wave stores nothing. nq_in: the word the round before
+  // wrote (nullptr: not maintained, or something wrote records, tile words, rows or options since:
+  // round_plan.h nq_ok): if it does not hold p.round, every tile of the network was quiescent in that
+  // round and is again in this one, so a leader wave adds the deferred +8 step to the kpend words of
+  // nq_group runs and every other wave returns at once. nq_rounds: rounds that took the path.
+  uint32_t* nq_out;
+  const uint32_t* nq_in;
+  uint32_t* nq_rounds;
+  uint32_t nq_group;  // 1..16 (option "net_quiet_group")
+  uint32_t nq_front;  // option "net_quiet_front": the leaders are the grid's first waves, not every nq_group-th
   uint32_t wave_dense; // k = 8 sweep (A/B option "wave_dense"): a wave with >= wave_dense lanes holding updates
                        // logs every such lane as a dense record (one store branch, no slot-word network); 0 off
 };

@@ -38,6 +38,9 @@ struct PlanKnobs {
   bool virtual_votes;
   uint32_t vv_min_bl;
   bool count_lazy, k_hi_virtual, ref_rows, uni_rows, ablate_gather, unsynced_shard;
+  // the network-quiet word (kernels.h nq_*): options "quiet_tiles" and "net_quiet"; count_changed: the
+  // sweep's counting build runs (option "count_changed"), which has no quiescent path
+  bool quiet_tiles = true, net_quiet = true, count_changed = false;
 };
 
 struct RoundPlan {
@@ -60,6 +63,10 @@ struct RoundPlan {
   // reference rows / uniform rows may be used; the caller clears these when no honest reference
   // node exists (ref_pick reads the device)
   bool ref_rows, uni_rows;
+  // the network-quiet word (kernels.h nq_*). net_quiet_out: the round maintains this round's word (a
+  // klazy sweep round of a single engine with quiet_tiles on); net_quiet_in: the word the round before
+  // wrote may be trusted (facts.nq_ok)
+  bool net_quiet_out, net_quiet_in;
 };
 
 struct RecordFacts {
@@ -86,6 +93,11 @@ struct RecordFacts {
   bool rflag_ok[3] = {false, false, false};
   // uni_ok[b]: buffer b was written by a sweep round that tagged its uniform-row slots
   bool uni_ok[3] = {false, false, false};
+  // the network-quiet word of the last round (kernels.h nq_in) says whether some run of that round was
+  // not quiescent, and nothing has written a record plane, a tile word, a validity word, a snapshot
+  // row or an option since: set by after_round of a klazy sweep round that maintained the word,
+  // cleared by everything else listed above k_round_sweep ("Network-quiet rounds")
+  bool nq_ok = false;
 
   // Anything but a reference-row sweep round that writes a snapshot buffer
   // (drop-in votes, adds, writes, init, validity/publish-rule refreshes, peer
@@ -93,6 +105,7 @@ struct RecordFacts {
   void snapshot_written() {
     rflag_ok[0] = rflag_ok[1] = rflag_ok[2] = false;
     uni_ok[0] = uni_ok[1] = uni_ok[2] = false;
+    nq_ok = false;
   }
   // av_init_records: every plane is rewritten (the caller clears the tile words of what was deferred).
   // Every record starts at count 0 with no considered vote (NewVoteRecord, vote.go:33-35), and a
@@ -108,6 +121,7 @@ struct RecordFacts {
   void add_targets() {
     warm_all = false;
     fresh = false;
+    nq_ok = false;
   }
   // drop-in votes: at most one confidence step per vote, so the most votes one node gets bound the
   // counts; a neutral vote shifts in consider = 0
@@ -115,17 +129,30 @@ struct RecordFacts {
     fresh = false;
     count_bound = (int)std::min<int64_t>(127, count_bound + max_node_votes);
     if (any_neutral) c_monotone = false;
+    nq_ok = false;
   }
   void write_records() {
+    nq_ok = false;
     c_monotone = false;
     fresh = false;
     count_bound = 127;  // arbitrary counts written
   }
-  void replay_call() { c_monotone = false; }  // replayed votes may be neutral
-  void votes_written_back() { v_stale = false; }
-  void counts_written_back() { k_pend = false; }
+  void replay_call() {  // replayed votes may be neutral
+    c_monotone = false;
+    nq_ok = false;
+  }
+  // a write-back zeroes the tile words (pend = 0), which the network-quiet path does not look at
+  void votes_written_back() {
+    v_stale = false;
+    nq_ok = false;
+  }
+  void counts_written_back() {
+    k_pend = false;
+    nq_ok = false;
+  }
   // the responders' re-adds (pub_mode 2) create records after the round's votes
   void responder_readds() {
+    nq_ok = false;
     warm_all = false;
     count_bound = 127;
   }
@@ -142,6 +169,8 @@ struct RecordFacts {
     fresh = false;
     rflag_ok[out_buf] = p.ref_rows && refw;
     uni_ok[out_buf] = p.uni_rows;
+    // (every other kind of round: non-klazy, replay, capped, first-generation, an engine with an exchange)
+    nq_ok = p.net_quiet_out;
     if (p.replay)
       warm_all = false;
     else if (c_monotone && p.k >= 8 && !p.capped && all_valid)
@@ -189,6 +218,10 @@ inline RoundPlan plan_round(const RecordFacts& f, const PlanShape& s, const Plan
   // uniform rows: a node-sharded engine sees every row only through the peer exchange, whose pushes
   // carry the slots (unsynced_shard, diagnostics: a rank's share alone, on its own slot)
   r.uni_rows = o.uni_rows && tagged && (s.NL == (uint32_t)s.N || s.peer_world > 1 || o.unsynced_shard);
+  // the network-quiet word: the single-engine build of the klazy sweep (no exchange, no counting); a
+  // round that cannot be uniform (no uniform rows) still maintains it, by tagging it in every wave
+  r.net_quiet_out = o.quiet_tiles && o.net_quiet && r.klazy && sweep && !o.count_changed && s.peer_world <= 1 && !s.has_comm;
+  r.net_quiet_in = r.net_quiet_out && f.nq_ok;
   return r;
 }
 

@@ -1181,6 +1181,62 @@ __device__ __forceinline__ uint32_t settled_run_uni(const RoundParams& p, uint32
 //  * peer pushes, the barrier's slot copy and RCCL gathers write snapshot buffers of node-sharded
 //    engines only: those run the CC build, which has no quiescent path.
 //
+// Network-quiet rounds (p.nq_in, option "net_quiet", default 1; the single-engine build of the walking
+// warm mode with runs, as the quiescent tiles). The induction: let every wave that owns tiles in round
+// r - 1 find its whole run quiescent (or round r - 1 take this path). Then round r - 1 stored no
+// snapshot row, no uniform tag, no plane, no validity word and no vstale word; every kpend word kept
+// kPendAllLive and its pend grew by one (>= 3 now). If round r is again a klazy round of the same
+// engine and nothing but reads happened in between, then in round r
+//  * the run geometry, the Byzantine words and the validity words are those of round r - 1: every run is
+//    free of Byzantine nodes and every tile a settled candidate (kVUniform, kPendAllLive), pend >= 2;
+//  * pref_in was not written by round r - 1: its rows are what pref_prev held (points (1)-(3) of the
+//    quiescent tiles say a quiescent tile would have stored the word already there), and the kernel
+//    still tests both uniform slots, which no round since has tagged;
+// so every tile is quiescent in round r by the three points above, and its one effect is pend + 1, the
+// applied votes and its 8 B. The word: a wave that owns tiles and is not quiescent throughout (general
+// tiles, the settled walk, settled_run, a Byzantine node in the run, a non-uniform snapshot, every
+// other mode of this kernel) stores the tag p.round + 1 into p.nq_out at its end; a quiescent wave and a
+// wave of this path store nothing. Round r reads round r - 1's word (the other of two, by round parity:
+// a wave of round r tagging the word that round r still reads would hide round r - 1's tag); a tag
+// from an older round is smaller than p.round (rounds only grow) and never reads as this one.
+// Who may invalidate the induction between two rounds, and where nq_ok (round_plan.h) is cleared:
+//  * every caller of facts.snapshot_written: av_set_valid, av_add_targets, av_register_votes(_batch),
+//    av_write_records, av_init_records (facts.init), av_set_option (every option: the run geometry, the
+//    path's own switches), av_set_polling, responder and exchange set-up, the replay launches;
+//  * every write-back (materialize in engine.cpp: av_materialize, and what any reader or writer of
+//    counts asks for first): kpend = 0, and this path does not test pend >= 2;
+//  * after_round of any round that did not maintain the word: non-klazy (the kconsume round, rounds
+//    near finalization), fresh, replay, capped and first-generation rounds, engines with an exchange
+//    or with count_changed (the CC build);
+//  * av_read_records, av_read_pref, av_census, the log readers and av_discard_updates write none of
+//    the above and leave nq_ok as it is.
+// The leader waves (G = p.nq_group; p.nq_front: the grid's first waves, else wave0 % G == 0) take G
+// consecutive runs: up to 256 kpend words, one lane per tile, all chunks requested before the first is
+// waited for. Counters as the per-run quiescent
+// path of settled_run_uni: 8 B per tile; 8 votes per polled record, every lane of every tile but the
+// network's last (possibly partial) tile being active.
+constexpr uint32_t kNqChunks = 4;  // 64 tiles each: G <= 16 runs of <= 16 tiles
+__device__ __forceinline__ void net_quiet_run(const RoundParams& p, uint32_t lane, uint32_t t0, uint32_t tile_end,
+                                              SweepAcc& acc) {
+  const uint32_t n = tile_end - t0;  // <= 256
+  const uint32_t vw = at_byte(p.valid, (lane & (p.BL - 1u)) * 4u);
+  uint32_t kw[kNqChunks];
+#pragma unroll
+  for (uint32_t c = 0; c < kNqChunks; ++c) kw[c] = c * 64u + lane < n ? p.kpend[t0 + c * 64u + lane] : 0u;
+  uint32_t mine = 0u;
+#pragma unroll
+  for (uint32_t c = 0; c < kNqChunks; ++c) {
+    if (c * 64u + lane < n) {
+      p.kpend[t0 + c * 64u + lane] = ((kw[c] & 0xFFu) + 1u) | kPendAllLive | (kw[c] & kHiVirt);
+      ++mine;
+    }
+  }
+  const uint32_t last = (p.Lpad >> 6) - 1u;
+  const bool cut = last < tile_end && last * 64u + lane >= p.L;  // (t0 <= last: the wave owns a tile)
+  acc.applied += 8u * (uint32_t)__popc(vw) * (n - (cut ? 1u : 0u));
+  acc.lane_bytes += 8u * mine;
+}
+
 // MODE: kModeWarm (sim, every consider plane all-ones), kModeCheck (sim, per
 // tile: the oldest consider plane decides), kModeReplay (replayed votes),
 // kModeAblate (kModeCheck with the peer gather replaced by a coalesced read of
@@ -1213,6 +1269,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == kMo
     acc.qpub = reinterpret_cast<uint32_t*>(s_dyn) + w * (kPushQ * 64u);
     acc.qpm = s_dyn + 4u * 4u * kPushQ * 64u + w * (kPushQ * 64u);
   }
+  // the network-quiet word of the round before (kernels.h nq_in), requested with the uniform slots
+  const uint32_t nqw = p.nq_in ? *p.nq_in : p.round;
   // uniform rows (kernels.h): no rank's slot of pref_in carries this round's tag
   bool uniform = p.uni_in != nullptr;
   if (uniform)
@@ -1224,6 +1282,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == kMo
     for (uint32_t r = 0; r < p.uni_world; ++r) prev_uni = prev_uni && p.uni_prev[r] != p.round - 1u;
   const bool uniform_prev = prev_uni && p.uni_votes && p.vv;
   const uint32_t uflags = (K == 8 && uniform && p.uni_votes && p.vv ? kUniVotes : 0u) | (uniform_prev ? kUniPrev : 0u);
+  // nq_tag: this wave owns tiles and some of them were not quiescent (kernels.h nq_out)
+  bool nq_tag = wave0 < tiles;
+  bool nq_taken = false;
+  if constexpr (MODE == kModeWarm && K == 8 && !CC) {
+    // Network-quiet round (above): every tile of the network is quiescent
+    if (nqw != p.round && prev_uni && p.tpw && p.quiet_tiles && p.lean && p.settled_fast && p.klazy && p.vv) {
+      const uint32_t G = min(max(p.nq_group, 1u), 16u), tpw = min(p.tpw, 16u);
+      // the leaders: every G-th wave, or (p.nq_front) the grid's first waves, which are dispatched first
+      // and work while the rest of the grid is dispatched and ends
+      if (!p.nq_front && wave0 % G) return;
+      const uint32_t t0 = (p.nq_front ? wave0 * G : wave0) * tpw;
+      if (t0 >= tiles) return;
+      net_quiet_run(p, lane, t0, min(t0 + G * tpw, tiles), acc);
+      if (wave0 == 0u && lane == 0u) atomicAdd(p.nq_rounds, 1u);
+      nq_taken = true;
+      nq_tag = false;
+    }
+  }
   if constexpr (MODE == kModeWarmPipe) {
     // software-pipelined: tile t + nwaves's loads (state, peer draw, gathers)
     // are in flight while tile t is computed
@@ -1236,7 +1312,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == kMo
       process_tile<K, false, true, POL, true>(p, tile, lane, cur, 0u, acc);
       cur = nxt;
     }
-  } else {
+  } else if (!nq_taken) {
     uint32_t tile = wave0, tile_end = tiles, stride = nwaves;
     WaveDraw wd;
     wd.ok = false;
@@ -1267,6 +1343,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == kMo
           if (wave0 % p.uni_merge) tile = tile_end = tiles;
           else tile_end = min(tile + p.tpw * p.uni_merge, tiles);
         }
+        nq_tag = tile < tiles;
         if (tile < tiles) {
           const uint32_t nlA = uni(div_bl(p, tile * 64u));
           const uint32_t nlB = uni(div_bl(p, min(tile_end * 64u, p.L) - 1u));
@@ -1310,6 +1387,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == kMo
 #endif
             uni_done = settled_run_uni<POL, CC>(p, lane, tile, tile_end, wd.meta, nlA, nn, upre, quiet, acc);
             uni_ran = true;
+            // (a run holding a Byzantine node comes back with no tile done)
+            if (quiet == all_tiles && uni_done == all_tiles) nq_tag = false;
           }
           const bool any_stale = __ballot((st & kVMask) == kVStale) != 0ull;
           if (uni_done != all_tiles) {
@@ -1463,6 +1542,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == kMo
     atomicAdd(&p.changed[kLogShards + acc.shard], (unsigned long long)acc.changed_segs);
   }
   if (p.count_changed && lane == 0 && acc.pushed) atomicAdd(&p.changed[2 * kLogShards + acc.shard], (unsigned long long)acc.pushed);
+  if (p.nq_out && nq_tag && lane == 0) *p.nq_out = p.round + 1u;  // not a quiescent wave (kernels.h nq_out)
   if (p.uni_out && __ballot(acc.umis != 0u) != 0ull && lane == 0) {
     // some word this wave published differs from the reference row: tag the output snapshot's slot
     // of this rank in every replica (read by the next round, after the barrier in a peer exchange)

@@ -97,7 +97,7 @@ EXPORTED = [
     "av_updates_digest_range", "av_read_pref_words", "av_set_polling",
     "av_register_votes_batch", "av_changed_words", "av_materialize", "av_peer_group_serial", "av_peer_sync",
     "av_pushed_words", "av_log_entries", "av_resize_log", "av_fetch_compact", "av_fetch_compact_async",
-    "av_fetch_compact_wait", "av_compact_expand", "av_update_round_shift",
+    "av_fetch_compact_wait", "av_compact_expand", "av_update_round_shift", "av_net_quiet_rounds",
 ]
 
 _lib = None
@@ -140,6 +140,7 @@ def lib():
         "av_applied_votes": (i32, [_vp, P(i64)]),
         "av_alg_bytes": (i32, [_vp, P(i64)]),
         "av_alg_bytes_reread": (i32, [_vp, P(i64)]),
+        "av_net_quiet_rounds": (i32, [_vp, P(i64)]),
         "av_changed_words": (i32, [_vp, P(i64), P(i64)]),
         "av_materialize": (i32, [_vp]),
         "av_finalized_count": (i32, [_vp, P(i64)]),
@@ -178,6 +179,8 @@ def lib():
         "av_update_round_shift": (i32, [_vp, P(i32)]),
     }
     for name, (res, args) in sig.items():
+        if name == "av_net_quiet_rounds" and os.environ.get("AVHIP_LIB") and not hasattr(L, name):
+            continue  # an A/B against a library built before the counter existed
         f = getattr(L, name)
         f.restype = res
         f.argtypes = args
@@ -573,6 +576,14 @@ class Engine:
         """Part of alg_bytes() that re-reads preference words already gathered in the same round."""
         out = C.c_int64(0)
         _check(lib().av_alg_bytes_reread(self._h, C.byref(out)))
+        return out.value
+
+    @property
+    def net_quiet_rounds(self):
+        """Rounds that found the whole network quiescent in the round before and skipped the per-run
+        work (option net_quiet); their bytes and results are the per-run path's."""
+        out = C.c_int64(0)
+        _check(lib().av_net_quiet_rounds(self._h, C.byref(out)))
         return out.value
 
     def changed_words(self):

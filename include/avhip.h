@@ -345,6 +345,11 @@ int av_alg_bytes(av_engine* e, int64_t* out);
  * minus this = the compulsory bytes (every word read or written once), a lower
  * bound on HBM traffic. Diagnostics; no reference counterpart. */
 int av_alg_bytes_reread(av_engine* e, int64_t* out);
+/* Rounds since creation that found the whole network quiescent in the round
+ * before them and skipped the per-run work (option "net_quiet").
+ * Their bytes and results are those of the per-run path, so only this counter
+ * tells them apart. Diagnostics; no reference counterpart. */
+int av_net_quiet_rounds(av_engine* e, int64_t* out);
 /* Published preference words that changed in sweep rounds since creation: a
  * word differs from the word of the snapshot buffer it overwrites (the snapshot
  * of two rounds before, which every peer replica holds). Counted in every round
@@ -414,6 +419,11 @@ int av_sample_peers(av_engine* e, int64_t round, int64_t n0, int64_t n1, int32_t
  * "quiet_tiles" (1: a settled tile with two deferred rounds behind it and two
  * uniform input snapshots takes its count step with no A-plane read and no
  * republished row; engines without an exchange; exact),
+ * "net_quiet" (1: a round after one in which every tile was quiescent, with
+ * nothing written in between, adds the count step to the tile words alone:
+ * a leader wave takes "net_quiet_group" runs (16; 1..16) and the other waves
+ * end at once; "net_quiet_front" (1: the leaders are the grid's first waves;
+ * 0: every "net_quiet_group"-th wave); needs "quiet_tiles"; exact),
  * "wave_dense" (0; n: a wave with >= n lanes holding updates logs them all as
  * dense records; exact, measured slower), "uniform_rows" (1: uniform-row
  * settled tests), "k_hi_virtual" (1: the K4..K7 count planes left unstored
