@@ -121,7 +121,7 @@ struct av_engine {
   uint32_t* log_count = nullptr;
   uint64_t* dlog = nullptr;          // dense lane records (kernels.h dense_words(k) u64 each)
   uint32_t* dlog_count = nullptr;
-  uint64_t* mlog = nullptr;          // medium lane records (kernels.h kMedMax: 2 u64 each)
+  uint64_t* mlog = nullptr;          // medium lane records (kernels.h med_rec_words: 4 u64 each)
   uint32_t* mlog_count = nullptr;
   uint32_t mlog_cap = 0;
   uint32_t* upd_count = nullptr;     // StatusUpdates emitted per shard (singles + dense bits)
@@ -1169,14 +1169,14 @@ int av_create(const av_config* cfg, av_engine** out) {
   // take any log_cap updates that go dense (8 B of capacity per update)
   const uint32_t dw = avk::dense_words((uint32_t)e->k);
   e->dense_min = avk::dense_min((uint32_t)e->k);
-  // k = 8 with slot records (kernels.h AVK_MED_S4): a lane goes dense from 4 slots with updates on
-  const uint32_t dense_least = e->k == 8 && AVK_MED_S4 ? 4u : e->dense_min;
+  // k = 8 (slot records, kernels.h): a lane goes dense from 4 slots with updates on
+  const uint32_t dense_least = e->k == 8 ? 4u : e->dense_min;
   e->dlog_cap = std::max<uint32_t>(e->log_cap / dense_least, 16);
   if ((he = dev_alloc(&e->dlog, (size_t)e->dlog_cap * e->log_shards * dw)) != hipSuccess) return hip_fail(he, "alloc log");
   if ((he = dev_alloc(&e->upd_count, avk::kLogShards)) != hipSuccess) return hip_fail(he, "alloc log");
   // a medium record holds >= 2 updates: log_cap / 2 records per shard (kernels.h med_rec_words: 32 B
   // slot records, 16 B per update of capacity). Only k = 8 kernels emit them (round_common.h
-  // emit_updates_med: the sweep, k_replay_fast): other engines keep a token 16 records per shard.
+  // emit_store_med: the sweep, k_replay_fast): other engines keep a token 16 records per shard.
   e->mlog_cap = e->k == 8 ? std::max<uint32_t>(e->log_cap / 2, 16) : 16u;
   if ((he = dev_alloc(&e->mlog, (size_t)e->mlog_cap * e->log_shards * avk::med_rec_words())) != hipSuccess)
     return hip_fail(he, "alloc log");

@@ -296,31 +296,15 @@ inline void bl_divider(uint32_t d, uint32_t& magic, uint32_t& sh1, uint32_t& sh2
 __host__ __device__ constexpr uint32_t dense_words(uint32_t k) { return (k + 5u) / 2u; }  // u64 words
 __host__ __device__ constexpr uint32_t dense_min(uint32_t k) { return dense_words(k); }   // updates
 
-// Medium lane records (k = 8 round kernels, round_common.h emit_store_med), two formats:
-//  * AVK_MED_S4 = 1 (default): a slot record of four u64 = u32 words [key lo, key hi (pack_update
-//    with the block's first target, slot 0, status 0), S (bits 0-7: slots with updates; bit 8
-//    kMedS4Died: the last word is the died plane), A (final accepted plane), E of the first, second,
-//    third and fourth slot with updates (zero past the last; the fourth is the died plane when
-//    flagged)]. Logged by a lane with >= 2 updates in at most 4 slots (at most 3 when a record of it
-//    was deleted this round); other lanes with >= 2 updates log a dense record. Expanded as a dense
-//    record over the slots S names.
-//  * AVK_MED_S4 = 0: a lane with 2..kMedMax StatusUpdates in one round (k <= 8) logs one medium
-// record of two u64: the key (pack_update with the block's first target, slot
-// 0, status 0) and a payload: bits [3:0] = n updates, then n 10-bit fields at
-// bit 4 + 10 i, each (slot << 7 | bit << 2 | status) = the update's offset
-// from the key (expanded word = key + (slot << 24) + (bit << 2) + status).
-#ifndef AVK_MED_S4
-#define AVK_MED_S4 1
-#endif
+// Medium lane records (k = 8 round kernels, round_common.h emit_store_med): a slot record of four
+// u64 = u32 words [key lo, key hi (pack_update with the block's first target, slot 0, status 0), S
+// (bits 0-7: slots with updates; bit 8 kMedS4Died: the last word is the died plane), A (final
+// accepted plane), E of the first, second, third and fourth slot with updates (zero past the last;
+// the fourth is the died plane when flagged)]. Logged by a lane with >= 2 updates in at most 4 slots
+// (at most 3 when a record of it was deleted this round); other lanes with >= 2 updates log a dense
+// record. Expanded as a dense record over the slots S names.
 constexpr uint32_t kMedS4Died = 1u << 8;
-__host__ __device__ constexpr uint32_t med_rec_words() { return AVK_MED_S4 ? 4u : 2u; }  // u64 per medium record
-constexpr uint32_t kMedMax = 6;
-__host__ __device__ constexpr uint32_t med_field(uint32_t slot, uint32_t bit, uint32_t status) {
-  return (slot << 7) | (bit << 2) | status;
-}
-__host__ __device__ inline uint64_t med_word(uint64_t key, uint32_t f) {
-  return key + ((uint64_t)(f >> 7) << 24) + ((uint64_t)((f >> 2) & 31u) << 2) + (f & 3u);
-}
+__host__ __device__ constexpr uint32_t med_rec_words() { return 4u; }  // u64 per medium record
 
 // Update-log entry (one StatusUpdate, avalanche.go:59-62):
 //   [63:S] round - log_base | [S-1:28] node | [27:24] slot | [23:2] target | [1:0] status

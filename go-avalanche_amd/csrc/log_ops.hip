@@ -72,11 +72,10 @@ __device__ __forceinline__ void for_each_dense(const uint32_t* w, uint32_t K, F&
   }
 }
 
-// Medium record (kernels.h). Slot record (AVK_MED_S4): the dense expansion over the slots its mask
-// names (A after slot j = A ^ parity of the later slots' updates); folded record: {key, payload}.
+// Medium (slot) record (kernels.h): the dense expansion over the slots its mask names (A after slot
+// j = A ^ parity of the later slots' updates).
 template <typename F>
 __device__ __forceinline__ void for_each_med(const uint64_t* rec, F&& f) {
-#if AVK_MED_S4
   const uint32_t* w = reinterpret_cast<const uint32_t*>(rec);
   const uint64_t key = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
   const uint32_t S = w[2], A = w[3];
@@ -95,11 +94,6 @@ __device__ __forceinline__ void for_each_med(const uint64_t* rec, F&& f) {
       f(key + ((uint64_t)slot[i] << 24) + ((uint64_t)bit << 2) + st);
     }
   }
-#else
-  const uint64_t key = rec[0], pl = rec[1];
-  const uint32_t n = (uint32_t)(pl & 15u);
-  for (uint32_t i = 0; i < n && i < kMedMax; ++i) f(med_word(key, (uint32_t)(pl >> (4u + 10u * i)) & 1023u));
-#endif
 }
 
 // node field of an update word: bits [28, round_shift)
@@ -217,17 +211,11 @@ __device__ __forceinline__ uint64_t entry_key(const EncodeParams& p, uint32_t ki
   }
   if (kind == 1) {
     constexpr uint32_t MW = med_rec_words();
-#if AVK_MED_S4
     const u32x4* q = reinterpret_cast<const u32x4*>(p.mlog + addr * MW);
     const u32x4 a = q[0], b = q[1];
     const uint32_t S = a[2];
     nu = (uint32_t)(__popc(b[0]) + __popc(b[1]) + __popc(b[2]) + ((S & kMedS4Died) ? 0 : __popc(b[3])));
     return (uint64_t)a[0] | ((uint64_t)a[1] << 32);
-#else
-    const uint64_t* r = p.mlog + addr * MW;
-    nu = min((uint32_t)(r[1] & 15u), kMedMax);
-    return r[0];
-#endif
   }
   const uint32_t* w = reinterpret_cast<const uint32_t*>(p.dlog + addr * dense_words(p.K));
   uint32_t c = 0;
@@ -375,7 +363,7 @@ __device__ __forceinline__ void cell_or(uint32_t* msk, uint32_t* hi, uint32_t* l
 struct RecRegs {
   uint32_t kind;  // 0 single word, 1 slot (medium) record, 2 dense record
   uint32_t key;   // low half of the key word (a single: of the update word: slot, target, status)
-  uint32_t E[8];  // updated records per slot (k <= 8); folded medium records (AVK_MED_S4 = 0): payload
+  uint32_t E[8];  // updated records per slot (k <= 8)
   uint32_t A, died;
 };
 
@@ -393,7 +381,6 @@ __device__ __forceinline__ void load_rec(const EncodeParams& p, uint64_t ref, Re
   if (r.kind == 0u) {
     r.key = (uint32_t)p.log[addr];
   } else if (r.kind == 1u) {
-#if AVK_MED_S4
     const u32x4* q = reinterpret_cast<const u32x4*>(p.mlog + addr * med_rec_words());
     const u32x4 x = q[0], y = q[1];
     r.key = x[0];
@@ -407,13 +394,6 @@ __device__ __forceinline__ void load_rec(const EncodeParams& p, uint64_t ref, Re
       const uint32_t i = (uint32_t)__popc(S & ((1u << j) - 1u));
       r.E[j] = ((S >> j) & 1u) && i < nw ? pick4(i, y[0], y[1], y[2], y[3]) : 0u;
     }
-#else
-    const uint64_t* q = p.mlog + addr * med_rec_words();
-    const uint64_t k0 = q[0], pl = q[1];
-    r.key = (uint32_t)k0;
-    r.E[0] = (uint32_t)pl;
-    r.E[1] = (uint32_t)(pl >> 32);
-#endif
   } else {
     const uint32_t* w = reinterpret_cast<const uint32_t*>(p.dlog + addr * dense_words(p.K));
     r.key = w[0];
@@ -434,18 +414,6 @@ __device__ __forceinline__ void fill_regs(const EncodeParams& p, const RecRegs& 
     return;
   }
   const uint32_t blk = (((r.key >> 2) & 0x3FFFFFu) - p.t0) >> 5;  // the key's target field: the block's first
-#if !AVK_MED_S4
-  if (r.kind == 1u) {
-    const uint64_t pl = (uint64_t)r.E[0] | ((uint64_t)r.E[1] << 32);
-    const uint32_t n = min((uint32_t)(pl & 15u), kMedMax);
-    for (uint32_t i = 0; i < n; ++i) {
-      const uint32_t fld = (uint32_t)(pl >> (4u + 10u * i)) & 1023u;
-      const uint32_t slot = fld >> 7, bit = (fld >> 2) & 31u, st = fld & 3u, m = 1u << bit;
-      cell_or(msk, hi, lo, slot * p.BL + blk, m, (st & 2u) ? m : 0u, (st & 1u) ? m : 0u);
-    }
-    return;
-  }
-#endif
   uint32_t par = 0u;  // A after slot j = A_final ^ parity of the later slots' updates (vote.go:77-91)
 #pragma unroll
   for (int j = 7; j >= 0; --j) {

@@ -527,32 +527,6 @@ __device__ __forceinline__ uint32_t emit_updates_flat(const RoundParams& p, uint
   return 8u * st_s + 8u * DW * st_d;
 }
 
-// StatusUpdate emission with medium records (p.med, k <= 8): every lane with
-// updates stores exactly one entry — a single packed word (1 update), a
-// medium record (2..kMedMax: key + 10 bits per update, kernels.h) or a dense
-// record (more) — at its rank among the wave's lanes of that kind, so each
-// kind is one contiguous run per wave written by one store instruction (the
-// dense record: three dwordx4). No per-update store loop: a medium lane folds
-// its updates into the payload in registers. Statuses as emit_updates_flat (A
-// after slot j = A_final, flipped back for the first of a record's two
-// updates; vote.go:77-91). Returns the bytes stored (wave-uniform).
-// E[j] for a per-lane slot j: a 3-level mux at K = 8 (7 selects on 3 masks instead of a 7-step
-// compare-and-select chain), the chain otherwise.
-template <int K>
-__device__ __forceinline__ uint32_t select_slot(const uint32_t (&E)[K], uint32_t j) {
-  if constexpr (K == 8) {
-    const bool b0 = (j & 1u) != 0u, b1 = (j & 2u) != 0u, b2 = (j & 4u) != 0u;
-    const uint32_t a0 = b0 ? E[1] : E[0], a1 = b0 ? E[3] : E[2], a2 = b0 ? E[5] : E[4], a3 = b0 ? E[7] : E[6];
-    const uint32_t c0 = b1 ? a1 : a0, c1 = b1 ? a3 : a2;
-    return b2 ? c1 : c0;
-  } else {
-    uint32_t cur = E[0];
-#pragma unroll
-    for (int t = 1; t < K; ++t) cur = j == (uint32_t)t ? E[t] : cur;
-    return cur;
-  }
-}
-
 // Lowest set bit's index, 0xFFFFFFFF for 0 (v_ffbl_b32 as is: no zero test and select around it)
 __device__ __forceinline__ uint32_t ffbl_u32(uint32_t x) {
   uint32_t r;
@@ -561,48 +535,28 @@ __device__ __forceinline__ uint32_t ffbl_u32(uint32_t x) {
 }
 // bit (b & 31) of x
 __device__ __forceinline__ uint32_t bfe1(uint32_t x, uint32_t b) { return __builtin_amdgcn_ubfe(x, b & 31u, 1u); }
-// E[j & 7] as a bit-select tree: 7 v_bfi_b32 on the sign-extended bits of j (no compare writing a lane
-// mask, so no VALU-wrote-SGPR wait states before the selects)
-template <int K>
-__device__ __forceinline__ uint32_t select_slot_bfi(const uint32_t (&E)[K], uint32_t j) {
-  if constexpr (K != 8) return select_slot<K>(E, j);
-  else {
-  const uint32_t m0 = (uint32_t)__builtin_amdgcn_sbfe((int)j, 0u, 1u);
-  const uint32_t m1 = (uint32_t)__builtin_amdgcn_sbfe((int)j, 1u, 1u);
-  const uint32_t m2 = (uint32_t)__builtin_amdgcn_sbfe((int)j, 2u, 1u);
-  const uint32_t a0 = (m0 & E[1]) | (~m0 & E[0]), a1 = (m0 & E[3]) | (~m0 & E[2]);
-  const uint32_t a2 = (m0 & E[5]) | (~m0 & E[4]), a3 = (m0 & E[7]) | (~m0 & E[6]);
-  const uint32_t c0 = (m1 & a1) | (~m1 & a0), c1 = (m1 & a3) | (~m1 & a2);
-  return (m2 & c1) | (~m2 & c0);
-  }
-}
 
-#ifndef AVK_MED_WALK
-#define AVK_MED_WALK 1
-#endif
-// StatusUpdate log stores (k = 8 slot-record path) non-temporal: the log is read only after the
-// round, so its lines need not displace the gathered preference rows in L2 / MALL (A/B,
-// profiles/r04/session11/ablognt.log: C4p -3.1 / -3.7 %, C4 -3.6 %, C4pb -1.7 % per epoch)
-#ifndef AVK_LOG_NT
-#define AVK_LOG_NT 1
-#endif
-
-// A/B build knob: lanes with at least this many updates log a dense record (0: the default, above
-// kMedMax; 2: no medium records, the walk that folds a lane's updates into one is never run)
-#ifndef AVK_MED_DENSE_MIN
-#define AVK_MED_DENSE_MIN 0
-#endif
-
-// The reservation half of emit_updates_med: per-lane update count, the wave's
-// per-kind totals and the three reserving atomics, issued but not waited for
-// (their results are read in emit_store_med). A caller that issues it before
-// its plane stores waits for the atomics' return only, not for those stores
-// (vmcnt counts in issue order: an atomic issued after the stores would make
-// the wave wait for every store of the tile first).
+// StatusUpdate emission of the k = 8 round kernels (the sweep, k_replay_fast), in two halves:
+// every lane with updates stores exactly one entry, at its rank among the wave's lanes of its kind,
+// so each kind is one contiguous run per wave. The kinds (kernels.h "Medium lane records"):
+//  * one update: a single packed word (8 B);
+//  * updates in at most 4 slots (3 if a record of the lane was deleted this round): a 32-byte slot
+//    record {key, slot mask | died flag, A_final, up to 4 E_j words in slot order (the 4th: the died
+//    plane when flagged)}; the slot words are compacted by a shift-in network, no per-update work;
+//  * more: a dense record (48 B, three dwordx4).
+// Statuses as emit_updates_flat (vote.go:77-91). The log stores are non-temporal: the log is read
+// only after the round, so its lines need not displace the gathered preference rows in L2 / MALL
+// (profiles/r04/session11/ablognt.log: C4p -3.1 / -3.7 %, C4 -3.6 %, C4pb -1.7 % per epoch).
+//
+// emit_reserve_med, the reservation half: per-lane update count, the wave's per-kind totals and the
+// three reserving atomics, issued but not waited for (their results are read in emit_store_med). A
+// caller that issues it before its plane stores waits for the atomics' return only, not for those
+// stores (vmcnt counts in issue order: an atomic issued after the stores would make the wave wait
+// for every store of the tile first).
 struct EmitRes {
   uint32_t tot_s, tot_m, tot_d;  // wave-uniform: lanes of each kind
   uint32_t raw;                  // lanes 0, 1, 2: the singles / medium / dense atomics' results (one VGPR)
-  uint32_t lk;                   // per lane (AVK_MED_S4): slots with updates (bits 0-7), kind (bits 8-9)
+  uint32_t lk;                   // per lane: slots with updates (bits 0-7), kind (bits 8-9)
   bool any;                      // wave-uniform: some lane has an update
 };
 
@@ -612,32 +566,12 @@ __device__ __forceinline__ uint32_t lane_updates8(const uint32_t* E, int K) {
   return c;
 }
 
-// Medium records, two formats (kernels.h kMedS4 selects; the log readers in log_ops.hip follow it):
-//  * AVK_MED_S4 = 1 (default): a lane whose updates lie in at most 4 slots (3 if a record of it was
-//    deleted this round) stores a 32-byte slot record {key, slot mask | died flag, A_final, up to 4
-//    E_j words in slot order (the 4th: the died plane when flagged)}: the slot words are compacted
-//    by a shift-in network, no per-update work at all;
-//  * AVK_MED_S4 = 0: a 16-byte record folding up to kMedMax updates into 10-bit fields, walked one
-//    update per step (the round-3 form, kept for A/B).
-constexpr uint32_t kLkSingle = 1u << 8, kLkMed = 2u << 8, kLkDense = 3u << 8;
-constexpr uint32_t kLkTwo = 1u << 10;  // a single-word lane with two updates (SMAX = 2)
+constexpr uint32_t kLkSingle = 1u << 8, kLkMed = 2u << 8, kLkDense = 3u << 8;  // EmitRes::lk kinds
 
-// SMAX (AVK_MED_S4, k = 8): a lane with at most SMAX updates logs them as single packed words (8 B
-// each) instead of a 32-B slot record. At 2 (round 6, build knob AVK_SINGLE_MAX for k_round_sweep)
-// two words take 16 B where the record took 32, and in conflicting rounds a third of the lanes have
-// exactly two updates (the pair's two targets flip together): C4p's log shrinks from 25.6 to 20.3 B
-// per lane. The store needs no per-update loop (the second update is the first's slot's next bit, or
-// the next slot's only bit). Measured level (C4p epoch 6.43-6.50 ms at 1 and 2, C4 3.58-3.65, C4pb
-// 6.49-6.52; profiles/r06/delivery/ab_smax.log): the storm rounds are not paced by the log's bytes,
-// and two words are two entries for the delivery encoder, so 1 stays the default.
-#ifndef AVK_SINGLE_MAX
-#define AVK_SINGLE_MAX 1
-#endif
-
-template <int K, int SMAX = 1>
+template <int K>
 __device__ __forceinline__ EmitRes emit_reserve_med(const RoundParams& p, uint32_t shard, uint32_t lane,
                                                     const uint32_t (&E)[K], uint32_t died, uint32_t& updates) {
-  static_assert(SMAX == 1 || SMAX == 2, "one or two single words per lane");
+  static_assert(K == 8, "slot records are the k = 8 format");
   EmitRes r;
   uint32_t any = 0;
 #pragma unroll
@@ -648,29 +582,21 @@ __device__ __forceinline__ EmitRes emit_reserve_med(const RoundParams& p, uint32
   r.lk = 0u;
   if (!r.any) return r;
   const uint32_t cnt = lane_updates8(E, K);
-#if AVK_MED_S4
   uint32_t nz = 0u;
 #pragma unroll
   for (int j = 0; j < K; ++j) nz |= (E[j] != 0u ? 1u : 0u) << j;
   const uint32_t ns = (uint32_t)__popc(nz);
   // (A/B option wave_dense: a wave with many lanes holding updates logs them all dense)
   const bool wd = p.wave_dense != 0u && (uint32_t)__popcll(__ballot(cnt != 0u)) >= p.wave_dense;
-  const bool two = !wd && SMAX >= 2 && cnt == 2u;
-  const bool single = !wd && (cnt == 1u || two);
-  const bool med = !wd && cnt > (uint32_t)SMAX && (ns <= 3u || (ns == 4u && died == 0u));
-  const bool dense = wd ? cnt != 0u : cnt > (uint32_t)SMAX && !med;
-  r.lk = nz | (single ? kLkSingle : med ? kLkMed : dense ? kLkDense : 0u) | (two ? kLkTwo : 0u);
-#else
-  (void)died;
-  const uint32_t dmin = AVK_MED_DENSE_MIN ? AVK_MED_DENSE_MIN : max(p.dense_min, kMedMax + 1u);
-  const bool dense = cnt >= dmin, med = !dense && cnt >= 2u, single = cnt == 1u;
-#endif
+  // (`|| false`: what is left of the retired two-words-per-lane variant; dropping it makes the
+  // compiler commute one scalar AND below, so it goes with the next change to this function)
+  const bool single = !wd && (cnt == 1u || false);
+  const bool med = !wd && cnt > 1u && (ns <= 3u || (ns == 4u && died == 0u));
+  const bool dense = wd ? cnt != 0u : cnt > 1u && !med;
+  r.lk = nz | (single ? kLkSingle : med ? kLkMed : dense ? kLkDense : 0u);
   r.tot_d = (uint32_t)__popcll(__ballot(dense));
   r.tot_m = (uint32_t)__popcll(__ballot(med));
   r.tot_s = (uint32_t)__popcll(__ballot(single));
-#if AVK_MED_S4
-  if constexpr (SMAX >= 2) r.tot_s += (uint32_t)__popcll(__ballot(two));  // words, not lanes
-#endif
   updates += wave_sum(cnt);
   if (p.ablate_emit == 1u) return r;  // diagnostics: the cost of the round without its log stores
   // one atomic instruction, lanes 0 / 1 / 2 reserving the singles / medium / dense runs
@@ -700,223 +626,67 @@ __device__ __forceinline__ EmitRes emit_reserve_med(const RoundParams& p, uint32
 }
 
 // The store half: every lane with updates stores its one entry at its rank among the wave's lanes
-// of its kind (see emit_updates_med). Returns the bytes stored (wave-uniform).
-template <int K, int SMAX = 1>
+// of its kind. Returns the bytes stored (wave-uniform).
+template <int K>
 __device__ __forceinline__ uint32_t emit_store_med(const RoundParams& p, uint32_t shard, uint32_t lane,
                                                    uint32_t node, uint32_t tbase, const uint32_t (&E)[K],
                                                    uint32_t A_final, uint32_t died, const EmitRes& r,
                                                    uint32_t round_rel) {
-  static_assert(K <= 8, "slot fits 3 bits of a medium field; two updates per record per round at most");
+  static_assert(K == 8, "slot records are the k = 8 format");
   if (!r.any || p.ablate_emit == 1u) return 0u;
-#if AVK_MED_S4
-  if constexpr (K == 8) {
-    const uint32_t kind = r.lk & (3u << 8), nz = r.lk & 0xFFu;
-    const bool dense = kind == kLkDense, med = kind == kLkMed, single = kind == kLkSingle;
-    const bool two = SMAX >= 2 && (r.lk & kLkTwo) != 0u;
-    const uint64_t dl = __ballot(dense), ml = __ballot(med), sl = __ballot(single);
-    const uint64_t tl = SMAX >= 2 ? __ballot(two) : 0ull;
-    const uint32_t base = (uint32_t)__builtin_amdgcn_readlane((int)r.raw, 0);
-    const uint32_t mbase = (uint32_t)__builtin_amdgcn_readlane((int)r.raw, 1);
-    const uint32_t dbase = (uint32_t)__builtin_amdgcn_readlane((int)r.raw, 2);
-    const uint32_t st_d = dbase >= p.dlog_cap ? 0u : min(r.tot_d, p.dlog_cap - dbase);
-    const uint32_t st_m = mbase >= p.mlog_cap ? 0u : min(r.tot_m, p.mlog_cap - mbase);
-    const uint32_t st_s = base >= p.log_cap ? 0u : min(r.tot_s, p.log_cap - base);
-    const bool ovf = st_d < r.tot_d || st_m < r.tot_m || st_s < r.tot_s;
-    const uint64_t key = pack_update(round_rel, node, 0u, tbase, 0u, p.round_shift);
-    const uint64_t mine = dense ? dl : med ? ml : sl;
-    uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mine >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mine, 0u));
-    if (SMAX >= 2 && single)  // the lower lanes' second words come first
-      rank += __builtin_amdgcn_mbcnt_hi((uint32_t)(tl >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tl, 0u));
-    if (dense) {
-      if (rank < st_d) {
-        constexpr uint32_t DW = dense_words(K);
-        uint64_t* const rec = p.dlog + ((size_t)shard * p.dlog_cap + dbase + rank) * DW;
-        u32x4* const q = reinterpret_cast<u32x4*>(rec);
-        pst4<AVK_LOG_NT>(q, u32x4{(uint32_t)key, (uint32_t)(key >> 32), E[0], E[1]});
-        pst4<AVK_LOG_NT>(q + 1, u32x4{E[2], E[3], E[4], E[5]});
-        pst4<AVK_LOG_NT>(q + 2, u32x4{E[6], E[7], A_final, died});
-      }
-    } else if (med || single) {  // (lanes without updates skip the network: a wave of dense lanes skips it)
-      // the first 4 slots with updates, in slot order: shift in from the last slot down
-      uint32_t o0 = 0u, o1 = 0u, o2 = 0u, o3 = 0u;
-#pragma unroll
-      for (int j = K - 1; j >= 0; --j) {
-        const bool h = E[j] != 0u;
-        o3 = h ? o2 : o3;
-        o2 = h ? o1 : o2;
-        o1 = h ? o0 : o1;
-        o0 = h ? E[j] : o0;
-      }
-      if (med) {
-        if (rank < st_m) {
-          const bool hasd = died != 0u;  // then at most 3 slots: the died plane takes the 4th word
-          u32x4* const q = reinterpret_cast<u32x4*>(p.mlog + ((size_t)shard * p.mlog_cap + mbase + rank) * 4u);
-          pst4<AVK_LOG_NT>(q, u32x4{(uint32_t)key, (uint32_t)(key >> 32), nz | (hasd ? kMedS4Died : 0u), A_final});
-          pst4<AVK_LOG_NT>(q + 1, u32x4{o0, o1, o2, hasd ? died : o3});
-        }
-      } else if (single && rank < st_s) {
-        // the first update: slot ffbl(nz), record ffbl(o0); status from A_final and died (vote.go:77-91)
-        const uint32_t j = ffbl_u32(nz), bit = ffbl_u32(o0);
-        uint32_t a = bfe1(A_final, bit);
-        uint64_t* const w = p.log + (size_t)shard * p.log_cap + base + rank;
-        if (SMAX >= 2 && two) {
-          // the second: o0's next bit (same slot), else the next slot's only bit. A record with both
-          // (the same bit in two slots: a flip and its flip back) had A_final ^ 1 after the first
-          const uint32_t rest = o0 & (o0 - 1u);
-          const uint32_t j2 = rest ? j : ffbl_u32(nz & (nz - 1u)), bit2 = ffbl_u32(rest ? rest : o1);
-          a ^= (j2 != j && bit2 == bit) ? 1u : 0u;
-          const uint32_t a2 = bfe1(A_final, bit2), d2 = bfe1(died, bit2);
-          const uint64_t word2 = key + ((uint64_t)j2 << 24) + ((uint64_t)bit2 << 2) + ((a2 << 1) | (~(a2 ^ d2) & 1u));
-          if (rank + 1u < st_s) {
-            if constexpr (AVK_LOG_NT) __builtin_nontemporal_store(word2, w + 1); else w[1] = word2;
-          }
-        }
-        const uint32_t d = bfe1(died, bit);
-        const uint32_t st = (a << 1) | (~(a ^ d) & 1u);
-        const uint64_t word = key + ((uint64_t)j << 24) + ((uint64_t)bit << 2) + st;
-        if constexpr (AVK_LOG_NT) __builtin_nontemporal_store(word, w); else *w = word;
-      }
-    }
-    if (__ballot(ovf) != 0ull) note_overflow(p, lane);
-    return 8u * st_s + 32u * st_m + 8u * dense_words(K) * st_d;
-  }
-#endif
-  const uint32_t cnt = lane_updates8(E, K);
-  const uint32_t dmin = AVK_MED_DENSE_MIN ? AVK_MED_DENSE_MIN : max(p.dense_min, kMedMax + 1u);
-  const bool dense = cnt >= dmin, med = !dense && cnt >= 2u, single = cnt == 1u;
+  const uint32_t kind = r.lk & (3u << 8), nz = r.lk & 0xFFu;
+  const bool dense = kind == kLkDense, med = kind == kLkMed, single = kind == kLkSingle;
   const uint64_t dl = __ballot(dense), ml = __ballot(med), sl = __ballot(single);
-  const uint32_t tot_d = r.tot_d, tot_m = r.tot_m, tot_s = r.tot_s;
   const uint32_t base = (uint32_t)__builtin_amdgcn_readlane((int)r.raw, 0);
   const uint32_t mbase = (uint32_t)__builtin_amdgcn_readlane((int)r.raw, 1);
   const uint32_t dbase = (uint32_t)__builtin_amdgcn_readlane((int)r.raw, 2);
-  const uint32_t st_d = dbase >= p.dlog_cap ? 0u : min(tot_d, p.dlog_cap - dbase);
-  const uint32_t st_m = mbase >= p.mlog_cap ? 0u : min(tot_m, p.mlog_cap - mbase);
-  const uint32_t st_s = base >= p.log_cap ? 0u : min(tot_s, p.log_cap - base);
-  const bool ovf = st_d < tot_d || st_m < tot_m || st_s < tot_s;
+  const uint32_t st_d = dbase >= p.dlog_cap ? 0u : min(r.tot_d, p.dlog_cap - dbase);
+  const uint32_t st_m = mbase >= p.mlog_cap ? 0u : min(r.tot_m, p.mlog_cap - mbase);
+  const uint32_t st_s = base >= p.log_cap ? 0u : min(r.tot_s, p.log_cap - base);
+  const bool ovf = st_d < r.tot_d || st_m < r.tot_m || st_s < r.tot_s;
   const uint64_t key = pack_update(round_rel, node, 0u, tbase, 0u, p.round_shift);
   const uint64_t mine = dense ? dl : med ? ml : sl;
   const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mine >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mine, 0u));
   if (dense) {
     if (rank < st_d) {
       constexpr uint32_t DW = dense_words(K);
-      uint32_t w[2 * DW];
-      w[0] = (uint32_t)key;
-      w[1] = (uint32_t)(key >> 32);
-#pragma unroll
-      for (int j = 0; j < K; ++j) w[2 + j] = E[j];
-      w[2 + K] = A_final;
-      w[3 + K] = died;
-#pragma unroll
-      for (uint32_t i = 4 + K; i < 2 * DW; ++i) w[i] = 0u;
       uint64_t* const rec = p.dlog + ((size_t)shard * p.dlog_cap + dbase + rank) * DW;
-      if constexpr (DW % 2u == 0u) {  // 16-B aligned records (k = 8: 48 B, three dwordx4)
-#pragma unroll
-        for (uint32_t i = 0; i < DW / 2u; ++i)
-          reinterpret_cast<u32x4*>(rec)[i] = u32x4{w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]};
-      } else {
-#pragma unroll
-        for (uint32_t i = 0; i < DW; ++i) rec[i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
-      }
+      u32x4* const q = reinterpret_cast<u32x4*>(rec);
+      pst4<true>(q, u32x4{(uint32_t)key, (uint32_t)(key >> 32), E[0], E[1]});
+      pst4<true>(q + 1, u32x4{E[2], E[3], E[4], E[5]});
+      pst4<true>(q + 2, u32x4{E[6], E[7], A_final, died});
     }
-  } else if (AVK_MED_WALK && K == 8) {
-    // T: records with two updates this round. The walk runs for the wave's largest count (one
-    // wave-uniform test per step, no exec-mask branches); lanes past their own count (and dense or
-    // update-less lanes) compute a field that is masked out. Per step: the next slot with updates
-    // when the current one is used up (a bit-select mux on the slot index, select_slot_bfi), its
-    // lowest update, the status from two planes fixed per walk (a = A after slot j, vote.go:77-91:
-    // A_final flipped back for the first of a record's two updates; status bit 0 = ~(a ^ died)).
-    uint32_t seen = 0u, T = 0u, nz = 0u;
+  } else if (med || single) {  // (lanes without updates skip the network: a wave of dense lanes skips it)
+    // the first 4 slots with updates, in slot order: shift in from the last slot down
+    uint32_t o0 = 0u, o1 = 0u, o2 = 0u, o3 = 0u;
 #pragma unroll
-    for (int j = 0; j < K; ++j) {
-      T |= seen & E[j];
-      seen |= E[j];
-      nz |= (E[j] != 0u ? 1u : 0u) << j;
-    }
-    const uint32_t cm = dense ? 0u : cnt;  // updates this lane folds into its payload
-    const uint32_t Ad = A_final ^ died;
-    uint32_t S = 0u, j = 0u, cur = 0u;
-    uint64_t pl = cnt;
-#pragma unroll
-    for (uint32_t q = 0; q < kMedMax; ++q) {
-      if (__ballot(q < cm) == 0ull) break;  // wave-uniform
-      const bool adv = cur == 0u;
-      const uint32_t jn = ffbl_u32(nz);
-      j = adv ? jn : j;
-      nz = adv ? nz & (nz - 1u) : nz;
-      cur = adv ? select_slot_bfi<K>(E, jn) : cur;
-      const uint32_t bit = ffbl_u32(cur);
-      cur &= cur - 1u;
-      const uint32_t first = T & ~S;  // records whose first of two updates is still ahead
-      S |= 1u << bit;
-      const uint32_t st = (bfe1(A_final ^ first, bit) << 1) | bfe1(~(Ad ^ first), bit);
-      const uint32_t f = (j << 7) | (bit << 2) | st;
-      pl |= (uint64_t)(q < cm ? f : 0u) << (4u + 10u * q);
+    for (int j = K - 1; j >= 0; --j) {
+      const bool h = E[j] != 0u;
+      o3 = h ? o2 : o3;
+      o2 = h ? o1 : o2;
+      o1 = h ? o0 : o1;
+      o0 = h ? E[j] : o0;
     }
     if (med) {
       if (rank < st_m) {
-        u32x4* rec = reinterpret_cast<u32x4*>(p.mlog + ((size_t)shard * p.mlog_cap + mbase + rank) * 2u);
-        *rec = u32x4{(uint32_t)key, (uint32_t)(key >> 32), (uint32_t)pl, (uint32_t)(pl >> 32)};
+        const bool hasd = died != 0u;  // then at most 3 slots: the died plane takes the 4th word
+        u32x4* const q = reinterpret_cast<u32x4*>(p.mlog + ((size_t)shard * p.mlog_cap + mbase + rank) * 4u);
+        pst4<true>(q, u32x4{(uint32_t)key, (uint32_t)(key >> 32), nz | (hasd ? kMedS4Died : 0u), A_final});
+        pst4<true>(q + 1, u32x4{o0, o1, o2, hasd ? died : o3});
       }
     } else if (single && rank < st_s) {
-      p.log[(size_t)shard * p.log_cap + base + rank] = med_word(key, (uint32_t)(pl >> 4) & 1023u);
-    }
-  } else if (cnt) {
-    // T: records with two updates this round; walk the updates in slot order
-    uint32_t seen = 0u, T = 0u, nz = 0u;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      T |= seen & E[j];
-      seen |= E[j];
-      nz |= (E[j] != 0u ? 1u : 0u) << j;
-    }
-    uint32_t S = 0u, j = 0u, cur = 0u;
-    uint64_t pl = cnt;  // payload: n, then one field per update
-#pragma unroll
-    for (uint32_t q = 0; q < kMedMax; ++q) {
-      if (q < cnt) {
-        if (cur == 0u) {  // next slot with updates
-          j = (uint32_t)__ffs(nz) - 1u;
-          nz &= nz - 1u;
-          cur = select_slot<K>(E, j);
-        }
-        const uint32_t bit = (uint32_t)__ffs(cur) - 1u;
-        cur &= cur - 1u;
-        const uint32_t m = 1u << bit;
-        const uint32_t a = ((A_final ^ (T & ~S)) >> bit) & 1u;  // A after slot j (vote.go:77-91)
-        S |= m;
-        const uint32_t st = (died & m) ? (a ? 3u : 0u) : (a ? 2u : 1u);
-        pl |= (uint64_t)med_field(j, bit, st) << (4u + 10u * q);
-      }
-    }
-    if (med) {
-      if (rank < st_m) {
-        u32x4* rec = reinterpret_cast<u32x4*>(p.mlog + ((size_t)shard * p.mlog_cap + mbase + rank) * 2u);
-        *rec = u32x4{(uint32_t)key, (uint32_t)(key >> 32), (uint32_t)pl, (uint32_t)(pl >> 32)};
-      }
-    } else if (rank < st_s) {
-      p.log[(size_t)shard * p.log_cap + base + rank] = med_word(key, (uint32_t)(pl >> 4) & 1023u);
+      // the update: slot ffbl(nz), record ffbl(o0); status from A_final and died (vote.go:77-91)
+      const uint32_t j = ffbl_u32(nz), bit = ffbl_u32(o0);
+      const uint32_t a = bfe1(A_final, bit);
+      uint64_t* const w = p.log + (size_t)shard * p.log_cap + base + rank;
+      const uint32_t d = bfe1(died, bit);
+      const uint32_t st = (a << 1) | (~(a ^ d) & 1u);
+      const uint64_t word = key + ((uint64_t)j << 24) + ((uint64_t)bit << 2) + st;
+      __builtin_nontemporal_store(word, w);
     }
   }
   if (__ballot(ovf) != 0ull) note_overflow(p, lane);
-  return 8u * st_s + 16u * st_m + 8u * dense_words(K) * st_d;
-}
-
-// StatusUpdate emission with medium records (p.med, k <= 8): every lane with
-// updates stores exactly one entry — a single packed word (1 update), a
-// medium record (2..kMedMax: key + 10 bits per update, kernels.h) or a dense
-// record (more) — at its rank among the wave's lanes of that kind, so each
-// kind is one contiguous run per wave written by one store instruction (the
-// dense record: three dwordx4). No per-update store loop: a medium lane folds
-// its updates into the payload in registers. Statuses as emit_updates_flat (A
-// after slot j = A_final, flipped back for the first of a record's two
-// updates; vote.go:77-91). Returns the bytes stored (wave-uniform).
-template <int K>
-__device__ __forceinline__ uint32_t emit_updates_med(const RoundParams& p, uint32_t shard, uint32_t lane,
-                                                     uint32_t node, uint32_t tbase, const uint32_t (&E)[K],
-                                                     uint32_t A_final, uint32_t died, uint32_t& updates,
-                                                     uint32_t round_rel) {
-  const EmitRes r = emit_reserve_med<K>(p, shard, lane, E, died, updates);
-  return emit_store_med<K>(p, shard, lane, node, tbase, E, A_final, died, r, round_rel);
+  return 8u * st_s + 32u * st_m + 8u * dense_words(K) * st_d;
 }
 
 __device__ __forceinline__ void count_stats(const RoundParams& p, uint32_t wave_id, uint32_t lane, uint32_t applied,

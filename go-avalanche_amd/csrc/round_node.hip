@@ -429,34 +429,6 @@ __global__ __launch_bounds__(MAXT) void k_replay_node(const RoundParams p) {
 // the next round's replayed votes are loaded while this round is computed.
 // Same round loop, hand-off to the exact pass (count >= 120), StatusUpdates,
 // published words and counters as k_replay_node.
-#ifndef AVK_REPLAY_LATE_REFILL
-#define AVK_REPLAY_LATE_REFILL 0
-#endif
-// A/B knob: the StatusUpdate pipeline's depth (k = 8): 1 = round r's entries stored in round r + 1
-// (two pending sets), 2 = in round r + 2 (four sets, loop unrolled four times), so that the wait for
-// the reserving atomic's result (vmcnt counts in issue order: also every load and store issued before
-// it) is for operations two rounds old
-// A/B knob: the near-finalization check (a workgroup barrier) every round instead of from round J on
-#ifndef AVK_REPLAY_ALWAYS_CHECK
-#define AVK_REPLAY_ALWAYS_CHECK 0
-#endif
-#ifndef AVK_REPLAY_VMWAIT
-#define AVK_REPLAY_VMWAIT 0
-#endif
-#ifndef AVK_REPLAY_BUF3
-#define AVK_REPLAY_BUF3 0
-#endif
-#ifndef AVK_REPLAY_PIPE3
-#define AVK_REPLAY_PIPE3 0
-#endif
-#ifndef AVK_REPLAY_PIPE3_LATE
-#define AVK_REPLAY_PIPE3_LATE 0
-#endif
-// (round 5, tools/fuse_probe.py --repeat 15, three alternations on one box: depth 2 3.52-3.53 us per
-// round against 3.69-3.73 at depth 1; profiles/r05/s11/ab_c2e.log)
-#ifndef AVK_REPLAY_EMIT_DEPTH
-#define AVK_REPLAY_EMIT_DEPTH 2
-#endif
 template <int K, bool NT>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void k_replay_fast(const RoundParams p) {
   __shared__ uint32_t wmax[2];
@@ -536,20 +508,22 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void k
   const uint32_t J = maxc >= 120u ? 0u : (120u - maxc + (uint32_t)K - 1u) / (uint32_t)K;
   uint32_t done = R, applied = 0u, upd = 0u, emitted = 0u, pubs = 0u;
   // The replayed votes are prefetched two rounds ahead into two register buffers, (wb0) for even
-  // rounds and (wb1) for odd ones (the loop is unrolled twice): a round refills its own buffer with
+  // rounds and (wb1) for odd ones: a round refills its own buffer with
   // round r + 2's votes as soon as it has read them, and no register is copied while a load into it
   // is in flight (a rotating copy made every round wait for the load issued at its start).
   // StatusUpdates (k = 8: one entry per lane): round r's log space is reserved at the end of round r
-  // and its entries stored after round r + 1's slot network, so the reserving atomics' round trip
-  // overlaps a round of compute; the pending reservations alternate between two sets of registers too.
+  // and its entries stored after round r + 2's slot network, so that the wait for the reserving
+  // atomic's result (vmcnt counts in issue order: also every load and store issued before it) is for
+  // operations two rounds old; the pending reservations rotate through four sets of registers (the
+  // loop is unrolled four times). (Round 5: 3.52-3.53 us per round against 3.69-3.73 with the
+  // entries stored one round later; profiles/r05/s11/ab_c2e.log)
   EmitRes pendA{}, pendB{};
   uint32_t EpA[K], EpB[K], ApA = 0u, ApB = 0u;
   const uint32_t shard = wave_id % p.log_shards;  // once (a runtime modulo is a long sequence)
-  // wb: this round's replayed votes; nb: the buffer refilled with round r + 2's (wb itself with two
-  // buffers; with three (AVK_REPLAY_BUF3) the one read last round, whose registers are free)
+  // wb: this round's replayed votes; nb: the buffer refilled with round r + 2's (wb itself)
   auto step = [&](uint32_t r, u32x4 (&wb)[RQ], u32x4 (&nb)[RQ], EmitRes& pc, uint32_t (&Ec)[K], uint32_t& Ac,
                   const EmitRes& pp, const uint32_t (&Ep)[K], uint32_t Ap) -> bool {
-    if (AVK_REPLAY_ALWAYS_CHECK || r >= J) {  // a record with count >= 120 may finalize (and leave the poll set) this round
+    if (r >= J) {  // a record with count >= 120 may finalize (and leave the poll set) this round
       const uint32_t nearfin = Kp[6] & Kp[5] & Kp[4] & Kp[3];
       if (__syncthreads_or(nearfin != 0u)) {  // workgroup-uniform
         done = r;
@@ -557,15 +531,6 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void k
       }
     }
     uint32_t ys[7 + K], ns[7 + K], cv[K];
-#if AVK_REPLAY_VMWAIT
-    // this round's votes were loaded two rounds ago, and at least the RQ loads of last round's refill
-    // were issued after them: vmcnt(RQ) retires them (vmcnt counts in issue order). The compiler's own
-    // wait, which merges the loop's paths (stores and atomics in lane-conditional blocks), asked for
-    // vmcnt(0) here, i.e. for the refill just issued too: one memory latency per round
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_waitcnt((RQ & 15) | (7 << 4) | (15 << 8) | ((RQ >> 4) << 14));
-    __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
     for (int j = 0; j < K; ++j) {
       const uint32_t wj = wb[j >> 1][(j & 1) * 2];
@@ -594,12 +559,9 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void k
     // reload round R - 1's, unused — so that the loaded registers need no merge copy, which would wait)
     // (no instruction crosses this point: the loads below are not hoisted above the buffer's last
     // reads, so the buffer and the loads' destinations can be the same registers across the loop)
-    auto refill = [&]() {
-      __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int i = 0; i < RQ; ++i) nb[i] = pld4<true>(rq + (size_t)min(r + 2u, R - 1u) * rstride + i * 64);
-    };
-    if (!(K == 8 && AVK_REPLAY_LATE_REFILL)) refill();
+    for (int i = 0; i < RQ; ++i) nb[i] = pld4<true>(rq + (size_t)min(r + 2u, R - 1u) * rstride + i * 64);
     // the round's update masks go straight into this round's pending set (no copy)
     uint32_t alive = ~0u, c[4] = {0u, 0u, 0u, 0u}, F = 0u, ap = 0u;
     const uint32_t low3[3] = {Kp[0], Kp[1], Kp[2]};
@@ -620,13 +582,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void k
     }
     if constexpr (K == 8) {
       pc = emit_reserve_med<K>(p, shard, lane, Ec, 0u, upd);
-      // AVK_REPLAY_LATE_REFILL: the refill issued after this round's reserving atomic, so that the
-      // store of round r - 1's entries below (which waits for round r - 1's atomic: vmcnt counts in
-      // issue order) does not also wait for the votes of round r + 1, loaded after that atomic
-      if (AVK_REPLAY_LATE_REFILL) refill();
-      if (r >= (uint32_t)AVK_REPLAY_EMIT_DEPTH)
-        emitted += emit_store_med<K>(p, shard, lane, node, p.t0 + b * 32u, Ep, Ap, 0u, pp,
-                                     p.round_rel + r - (uint32_t)AVK_REPLAY_EMIT_DEPTH);
+      if (r >= 2u) emitted += emit_store_med<K>(p, shard, lane, node, p.t0 + b * 32u, Ep, Ap, 0u, pp, p.round_rel + r - 2u);
       Ac = A;
     } else {
       (void)pc;
@@ -638,147 +594,6 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void k
     }
     return true;
   };
-#if AVK_REPLAY_PIPE3
-  if constexpr (K == 8) {
-    // The emission one step later still: round q's update masks are made in step q, its log space
-    // reserved at the start of step q + 1 and its entries stored at the start of step q + 2, beside
-    // the refill. Every memory operation of a step is then issued before its slot network, so that
-    // when the next step's head waits for everything outstanding (the compiler's vmcnt(0) there:
-    // stores and atomics sit in lane-conditional blocks), those operations are a whole step old.
-    // Three vote buffers and three (E, A, reservation) sets, the loop unrolled three times.
-    EmitRes RX{}, RY{}, RZ{};
-    uint32_t EX[K], EY[K], EZ[K], AX = 0u, AY = 0u, AZ = 0u;
-    u32x4 wb2[RQ];
-    auto stepP = [&](uint32_t r, u32x4 (&wb)[RQ], u32x4 (&nb)[RQ], uint32_t (&Ec)[K], uint32_t& Ac,
-                     const uint32_t (&Er)[K], EmitRes& Rr, const uint32_t (&Es)[K], uint32_t As,
-                     const EmitRes& Rs) -> bool {
-      if (r >= J) {
-        const uint32_t nearfin = Kp[6] & Kp[5] & Kp[4] & Kp[3];
-        if (__syncthreads_or(nearfin != 0u)) {
-          done = r;
-          return false;
-        }
-      }
-      uint32_t ys[7 + K], ns[7 + K], cv[K];
-#pragma unroll
-      for (int j = 0; j < K; ++j) {
-        const uint32_t wj = wb[j >> 1][(j & 1) * 2];
-        cv[j] = wb[j >> 1][(j & 1) * 2 + 1];
-        const uint32_t yw = wj & cv[j];  // err == 0 implies considered (vote.go:55-56)
-        ys[7 + j] = yw;
-        ns[7 + j] = ~yw & cv[j];
-      }
-#pragma unroll
-      for (int i = 0; i < 7; ++i) {
-        ys[i] = V[6 - i] & C[6 - i];
-        ns[i] = ~V[6 - i] & C[6 - i];
-      }
-#pragma unroll
-      for (int i = 7; i >= 0; --i) {
-        V[i] = i < K ? ys[6 + K - i] : V[i - K];
-        if (i < K) {
-          uint32_t cc;
-          asm volatile("v_mov_b32 %0, %1" : "=v"(cc) : "v"(cv[K - 1 - i]));
-          C[i] = cc;
-        } else {
-          C[i] = C[i - K];
-        }
-      }
-      // round r - 2's entries first: their wait for its reservation (made a step ago; vmcnt counts in
-      // issue order) then covers nothing issued in this step; then round r - 1's reservation and the
-      // refill, which the next step's head waits for a whole step later
-      if (r >= 2u) emitted += emit_store_med<K>(p, shard, lane, node, p.t0 + b * 32u, Es, As, 0u, Rs, p.round_rel + r - 2u);
-      if (r >= 1u) Rr = emit_reserve_med<K>(p, shard, lane, Er, 0u, upd);  // round r - 1
-#if !AVK_REPLAY_PIPE3_LATE
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < RQ; ++i) nb[i] = pld4<true>(rq + (size_t)min(r + 2u, R - 1u) * rstride + i * 64);
-      __builtin_amdgcn_sched_barrier(0);
-#endif
-      uint32_t alive = ~0u, c[4] = {0u, 0u, 0u, 0u}, F = 0u, ap = 0u;
-      const uint32_t low3[3] = {Kp[0], Kp[1], Kp[2]};
-      round_slots<K, false>(ys, ns, low3, 0u, false, alive, A, Ec, c, F, ap);
-      applied += (uint32_t)K * 32u;
-      uint32_t cy = 0u;
-#pragma unroll
-      for (int i = 0; i < 7; ++i) {
-        const uint32_t ci = i < 4 ? c[i] : 0u;
-        const uint32_t t = Kp[i] ^ ci;
-        const uint32_t si = t ^ cy;
-        cy = (t & cy) | (Kp[i] & ci);
-        Kp[i] = (F & ci) | (~F & si);
-      }
-      if (r + 3u >= R) {  // the last three rounds fill the three snapshot buffers
-        p.pref_ring[(p.ring_next + r) % 3u][prow] = byz ? byz_pattern(p.round + r + 1u) : A;
-        ++pubs;
-      }
-#if AVK_REPLAY_PIPE3_LATE
-      // the refill as the step's last memory operations: whatever else the step issued (stores and
-      // atomics in lane-conditional blocks), at least these RQ loads follow the buffer the next step
-      // reads, on every path
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < RQ; ++i) nb[i] = pld4<true>(rq + (size_t)min(r + 2u, R - 1u) * rstride + i * 64);
-#endif
-      Ac = A;
-      return true;
-    };
-    for (uint32_t r = 0; r < R; r += 3u) {
-      if (!stepP(r, wb0, wb2, EX, AX, EZ, RZ, EY, AY, RY)) break;
-      if (r + 1u >= R || !stepP(r + 1u, wb1, wb0, EY, AY, EX, RX, EZ, AZ, RZ)) break;
-      if (r + 2u >= R || !stepP(r + 2u, wb2, wb1, EZ, AZ, EY, RY, EX, AX, RX)) break;
-    }
-    // rounds done - 2 (reserved, not stored) and done - 1 (neither)
-    const uint32_t tb = p.t0 + b * 32u;
-    if (done >= 2u) {
-      const uint32_t q = done - 2u, rk = p.round_rel + q;
-      if (q % 3u == 0u) emitted += emit_store_med<K>(p, shard, lane, node, tb, EX, AX, 0u, RX, rk);
-      else if (q % 3u == 1u) emitted += emit_store_med<K>(p, shard, lane, node, tb, EY, AY, 0u, RY, rk);
-      else emitted += emit_store_med<K>(p, shard, lane, node, tb, EZ, AZ, 0u, RZ, rk);
-    }
-    if (done >= 1u) {
-      const uint32_t q = done - 1u, rk = p.round_rel + q;
-      if (q % 3u == 0u) {
-        RX = emit_reserve_med<K>(p, shard, lane, EX, 0u, upd);
-        emitted += emit_store_med<K>(p, shard, lane, node, tb, EX, AX, 0u, RX, rk);
-      } else if (q % 3u == 1u) {
-        RY = emit_reserve_med<K>(p, shard, lane, EY, 0u, upd);
-        emitted += emit_store_med<K>(p, shard, lane, node, tb, EY, AY, 0u, RY, rk);
-      } else {
-        RZ = emit_reserve_med<K>(p, shard, lane, EZ, 0u, upd);
-        emitted += emit_store_med<K>(p, shard, lane, node, tb, EZ, AZ, 0u, RZ, rk);
-      }
-    }
-  } else {
-#endif
-#if AVK_REPLAY_BUF3
-  // three replayed-vote buffers and three pending sets, the loop unrolled three times: round r reads
-  // buffer r % 3 and refills buffer (r + 2) % 3 (read in round r - 1: its registers are dead, so the
-  // loads need no copy into the loop header's registers, which waited for them); it reserves into set
-  // r % 3 and stores set (r - depth) % 3
-  u32x4 wb2[RQ];
-  EmitRes pendC{};
-  uint32_t EpC[K], ApC = 0u;
-  constexpr bool D2 = AVK_REPLAY_EMIT_DEPTH == 2;
-  for (uint32_t r = 0; r < R; r += 3u) {
-    if (!(D2 ? step(r, wb0, wb2, pendA, EpA, ApA, pendB, EpB, ApB) : step(r, wb0, wb2, pendA, EpA, ApA, pendC, EpC, ApC))) break;
-    if (r + 1u >= R ||
-        !(D2 ? step(r + 1u, wb1, wb0, pendB, EpB, ApB, pendC, EpC, ApC) : step(r + 1u, wb1, wb0, pendB, EpB, ApB, pendA, EpA, ApA)))
-      break;
-    if (r + 2u >= R ||
-        !(D2 ? step(r + 2u, wb2, wb1, pendC, EpC, ApC, pendA, EpA, ApA) : step(r + 2u, wb2, wb1, pendC, EpC, ApC, pendB, EpB, ApB)))
-      break;
-  }
-  if constexpr (K == 8) {  // the last rounds run's entries (rounds done - depth .. done - 1)
-    for (uint32_t q = done >= (uint32_t)AVK_REPLAY_EMIT_DEPTH ? done - (uint32_t)AVK_REPLAY_EMIT_DEPTH : 0u; q < done; ++q) {
-      const uint32_t sset = q % 3u;
-      const uint32_t rk = p.round_rel + q;
-      if (sset == 0u) emitted += emit_store_med<K>(p, shard, lane, node, p.t0 + b * 32u, EpA, ApA, 0u, pendA, rk);
-      else if (sset == 1u) emitted += emit_store_med<K>(p, shard, lane, node, p.t0 + b * 32u, EpB, ApB, 0u, pendB, rk);
-      else emitted += emit_store_med<K>(p, shard, lane, node, p.t0 + b * 32u, EpC, ApC, 0u, pendC, rk);
-    }
-  }
-#elif AVK_REPLAY_EMIT_DEPTH == 2
   // four pending sets: round r reserves into set r % 4 and stores set (r - 2) % 4; the replayed-vote
   // buffers keep alternating (r % 2)
   EmitRes pendC{}, pendD{};
@@ -799,22 +614,6 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void k
       else emitted += emit_store_med<K>(p, shard, lane, node, p.t0 + b * 32u, EpD, ApD, 0u, pendD, rk);
     }
   }
-#else
-  for (uint32_t r = 0; r < R; r += 2u) {
-    if (!step(r, wb0, wb0, pendA, EpA, ApA, pendB, EpB, ApB)) break;
-    if (r + 1u >= R || !step(r + 1u, wb1, wb1, pendB, EpB, ApB, pendA, EpA, ApA)) break;
-  }
-  if constexpr (K == 8) {  // the last round run's entries (round done - 1)
-    if (done > 0u) {
-      const bool odd = ((done - 1u) & 1u) != 0u;
-      emitted += odd ? emit_store_med<K>(p, shard, lane, node, p.t0 + b * 32u, EpB, ApB, 0u, pendB, p.round_rel + done - 1u)
-                     : emit_store_med<K>(p, shard, lane, node, p.t0 + b * 32u, EpA, ApA, 0u, pendA, p.round_rel + done - 1u);
-    }
-  }
-#endif
-#if AVK_REPLAY_PIPE3
-  }
-#endif
   if (done < R && b == 0) p.node_flags[nl] = done + 1u;  // the exact pass takes rounds done..R-1
   if (done > 0u) {
     pst4<NT>(grp, u32x4{V[0], V[1], V[2], V[3]});

@@ -37,26 +37,16 @@
 #include "round_plan.h"
 #include "round_slots.h"
 
-// A/B build knob: the StatusUpdate log reservation issued before the tile's stores (1) or after
-// them, inside the emission (0)
-#ifndef AVK_EMIT_HOIST
-#define AVK_EMIT_HOIST 1
-#endif
-// A/B build knob: compile the per-phase ablation diagnostics (option "ablate_phase") into the warm
+// Build knob: compile the per-phase ablation diagnostics (option "ablate_phase") into the warm
 // path (1: the Makefile's "ablate" variant library only; the product kernel is built without them)
 #ifndef AVK_ABLATE_PHASE
 #define AVK_ABLATE_PHASE 0
 #endif
-// A/B build knob: in rounds that count changed words (peer pushes), the overwritten published words
-// are loaded ahead of time with the tile (1) or by each publish (0)
-// (0: the prefetched words' registers spilled in the counting build: C4 epoch 7.40 ms against 5.95,
-// C4p 24.0 against 15.4 with count_changed on, profiles/r04/ab_count_changed.log)
-#ifndef AVK_CC_PREFETCH
-#define AVK_CC_PREFETCH 0
-#endif
 // A/B build knob: the storm path's publish loads (overwritten word, stale and need bytes) issued
 // before the tile's plane stores (1) or by publish itself, after them (0, default: measured 3 % faster
 // on masked C4p node shards at 8 ranks, profiles/r06/ab_pub_preload.log)
+// (decided, but kept: taking its losing side out changes the counting k = 8 kernels' register
+// allocation, so it goes with the next change to publish)
 #ifndef AVK_PUB_PRELOAD
 #define AVK_PUB_PRELOAD 0
 #endif
@@ -108,8 +98,8 @@ __device__ __forceinline__ void push_word(const RoundParams& p, uint32_t* dst, u
 // (system-scope write-through stores over xGMI; the barrier after the round orders them before any
 // peer reads them). Changed words are counted when p.count_changed (the push volume),
 // per wave by ballot (a scalar: a per-lane counter live across the tile loop spilled).
-// `old`: the overwritten word when the caller knows it (`known`: loaded ahead of time, or implied by
-// the tile's history, below); else it is loaded here (its latency then sits on the tile's chain).
+// `old`: the overwritten word when the caller knows it (`known`: implied by the tile's history,
+// below); else it is loaded here, or ahead by the caller (`pre`, AVK_PUB_PRELOAD).
 // A tile whose count steps were deferred in the two rounds before this one (kpend >= 2) kept its
 // accepted plane through them, so an honest row it publishes unchanged this round equals the
 // snapshot being overwritten (written three rounds ago): no load, no push; a Byzantine row's word
@@ -148,7 +138,7 @@ __device__ __forceinline__ void publish(const RoundParams& p, uint32_t prow, uin
                                         const PubPre* pre = nullptr) {
   if (CC && p.count_changed) {
     const bool pl = pre && pre->have;  // loaded ahead (an unknown word only)
-    if (!known && !AVK_CC_PREFETCH) old = pl ? pre->old : p.pref_out[prow];
+    if (!known) old = pl ? pre->old : p.pref_out[prow];
     uint32_t nm = p.peer_all, st = 0u, si = 0u;
     if (p.stale) {
       si = nl * p.segs + ((prow - (p.n0 + nl) * p.PS) >> 5);
@@ -230,7 +220,8 @@ struct TileIn {
   uint32_t kw;                   // wave-uniform: kpend[tile] (kernels.h klazy); K planes not loaded if all-live
   uint32_t C[WARM ? 1 : 8];
   uint32_t uref;                 // uniform rows (p.uni_out): ref_node's word of pref_in for the lane's block
-  uint32_t old;                  // p.count_changed: the word of pref_out this lane's published word overwrites
+  uint32_t old;                  // always 0 (was a retired variant's prefetched word): removing the field moves w
+                                 // and cw and reorders the pipelined kernels' loop set-up; it goes with their next change
   uint32_t w[K];                 // yes bits: err == 0 (vote.go:55)
   uint32_t cw[REPLAY ? K : 1];   // consider bits: int32(err) >= 0 (vote.go:56); sim votes: all-ones
 };
@@ -348,7 +339,7 @@ __device__ __forceinline__ void load_tile(const RoundParams& p, uint32_t tile, u
   // loaded with the tile (an in-order vmcnt wait for it late in the step would also wait for the
   // step's plane stores)
   in.uref = p.uni_out ? p.pref_in[p.ref_node * p.PS + x.b] : 0u;
-  in.old = AVK_CC_PREFETCH && CC && p.count_changed ? p.pref_out[x.node * p.PS + x.b] : 0u;  // (publish)
+  in.old = 0u;
   if constexpr (REPLAY) {
     replay_load<K>(p.replay, x.gc, in.w, in.cw);
   } else {
@@ -633,12 +624,10 @@ __device__ __forceinline__ void process_tile(const RoundParams& p, uint32_t tile
   }
   // count_new = F ? c : count + c on planes 0..6 (survivors stay <= 127); deleted: count 128 (K7 set)
   const uint32_t died = P0 & ~alive;
-#if AVK_EMIT_HOIST
   // StatusUpdate log reservation (k = 8) before this tile's plane and published-word stores, so that
   // reading the atomics' results waits for them alone, not for those stores (round_common.h)
   EmitRes er{};
-  if constexpr (K == 8) er = emit_reserve_med<K, AVK_SINGLE_MAX>(p, acc.shard, lane, E, died, acc.updates);
-#endif
+  if constexpr (K == 8) er = emit_reserve_med<K>(p, acc.shard, lane, E, died, acc.updates);
   {
     uint32_t cy = 0u;
 #pragma unroll
@@ -660,7 +649,7 @@ __device__ __forceinline__ void process_tile(const RoundParams& p, uint32_t tile
   if (K == 8 && p.hivirt && ((!WARM && p.fresh) || (klazy && (in.kw & kHiVirt))))
     hv = kdefer || __ballot(active && ((Kp[4] | Kp[5] | Kp[6] | died) != 0u)) == 0ull;
   if (active && !(kAblatePhase && KLZ_ABLATE && (p.ablate_phase & 4u))) {
-    const bool known = AVK_CC_PREFETCH || (kdefer && pend >= 2u);  // (publish)
+    const bool known = kdefer && pend >= 2u;  // (publish)
     PubPre pre{0u, 0u, 0u, false};
     if (AVK_PUB_PRELOAD && CC && p.count_changed && !known) pre = publish_loads(p, node * p.PS + b, node - p.n0);
     if (!kdefer) {
@@ -677,8 +666,7 @@ __device__ __forceinline__ void process_tile(const RoundParams& p, uint32_t tile
     const uint32_t prow = node * p.PS + b;  // < N * PS < 2^31
     const uint32_t pub = nbyz ? byz_pattern(p.round + 1u) : A;
     if (p.uni_out) acc.umis |= pub != in.uref ? 1u : 0u;  // uniform rows (kernels.h)
-    publish<POL, CC>(p, prow, pub, AVK_CC_PREFETCH ? in.old : (nbyz ? byz_pattern(p.round - 2u) : pub), acc,
-                     known, node - p.n0, acc.qslot, &pre);
+    publish<POL, CC>(p, prow, pub, nbyz ? byz_pattern(p.round - 2u) : pub, acc, known, node - p.n0, acc.qslot, &pre);
     // a record deleted this round keeps the vote/consider planes stored
     // above: K7 marks it dead, every reader masks by K7 (k_read_records,
     // k_add_targets resets all planes) and the next round's store zeroes them
@@ -716,11 +704,7 @@ __device__ __forceinline__ void process_tile(const RoundParams& p, uint32_t tile
   // k = 8: single words, medium and dense records, one contiguous entry per lane (round_common.h)
   uint32_t emitted;
   if constexpr (K == 8)
-#if AVK_EMIT_HOIST
-    emitted = emit_store_med<K, AVK_SINGLE_MAX>(p, acc.shard, lane, node, p.t0 + b * 32u, E, A, died, er, p.round_rel);
-#else
-    emitted = emit_updates_med<K>(p, acc.shard, lane, node, p.t0 + b * 32u, E, A, died, acc.updates, p.round_rel);
-#endif
+    emitted = emit_store_med<K>(p, acc.shard, lane, node, p.t0 + b * 32u, E, A, died, er, p.round_rel);
   else
     emitted = emit_updates<K>(p, tile, lane, node, p.t0 + b * 32u, E, A, died, acc.updates);
 
@@ -775,7 +759,6 @@ __device__ __forceinline__ bool settled_tile(const RoundParams& p, uint32_t tile
   const __amdgpu_buffer_rsrc_t ta =
       __builtin_amdgcn_make_buffer_rsrc(p.planes + (size_t)tile * (kPlanes * 64u), 0, kPlanes * 64 * 4, kRsrcWord3);
   const uint32_t A = __builtin_amdgcn_raw_buffer_load_b32(ta, (1536u + lane) * 4u, 0, POL > 0 ? 2 : 0);
-  const uint32_t old = AVK_CC_PREFETCH && CC && p.count_changed ? p.pref_out[(p.n0 + nl) * p.PS + b] : 0u;  // (publish)
   const uint32_t P0 = active ? at_byte(p.valid, b * 4u) : 0u;  // polled = live (kPendAllLive) and valid
   const uint32_t uref = p.uni_out ? p.pref_in[p.ref_node * p.PS + b] : 0u;  // uniform rows (kernels.h)
   uint32_t rows[8];
@@ -811,9 +794,8 @@ __device__ __forceinline__ bool settled_tile(const RoundParams& p, uint32_t tile
   if (active) {
     if (p.uni_out) acc.umis |= pub != uref ? 1u : 0u;
     const uint32_t prow = node * p.PS + b;  // < N * PS < 2^30 (sweep gate)
-    const bool known = AVK_CC_PREFETCH || (kw & 0xFFu) >= 2u;  // (publish)
-    publish<POL, CC>(p, prow, pub, AVK_CC_PREFETCH ? old : (is_byz(p.byz, node) ? byz_pattern(p.round - 2u) : pub),
-                     acc, known, nl, acc.qslot);
+    const bool known = (kw & 0xFFu) >= 2u;  // (publish)
+    publish<POL, CC>(p, prow, pub, is_byz(p.byz, node) ? byz_pattern(p.round - 2u) : pub, acc, known, nl, acc.qslot);
   }
   if (REF && p.rflag_out) ref_flag_store(p, lane, active, b, node, pub, p.pref_in[p.ref_node * p.PS + (active ? b : 0u)]);
   if (lane == 0) p.kpend[tile] = ((kw & 0xFFu) + 1u) | kPendAllLive | (kw & kHiVirt);
@@ -877,7 +859,6 @@ __device__ __forceinline__ uint32_t settled_run(const RoundParams& p, uint32_t l
     const uint32_t g = tile * 64u + lane;
     const bool active = g < p.L;
     const uint32_t nl = (active ? g : p.L - 1u) >> p.bl_log2;
-    const uint32_t old = AVK_CC_PREFETCH && CC && p.count_changed ? p.pref_out[(p.n0 + nl) * p.PS + b] : 0u;  // (publish)
     const uint32_t P0 = active ? vw : 0u;  // polled = live (kPendAllLive) and valid
     const uint32_t rel = nl - wd.nlA;
     uint32_t rows[8];
@@ -916,9 +897,8 @@ __device__ __forceinline__ uint32_t settled_run(const RoundParams& p, uint32_t l
     if (active) {
       umis |= pub != rin ? 1u : 0u;
       const uint32_t prow = node * p.PS + b;  // < N * PS < 2^30 (sweep gate)
-      const bool known = AVK_CC_PREFETCH || (m & 0xFFu) >= 2u;  // (publish)
-      publish<POL, CC>(p, prow, pub, AVK_CC_PREFETCH ? old : (((byzm >> rel) & 1ull) ? byz_pattern(p.round - 2u) : pub),
-                       acc, known, nl, i);
+      const bool known = (m & 0xFFu) >= 2u;  // (publish)
+      publish<POL, CC>(p, prow, pub, ((byzm >> rel) & 1ull) ? byz_pattern(p.round - 2u) : pub, acc, known, nl, i);
     }
     if (REF && p.rflag_out) ref_flag_store(p, lane, active, b, node, pub, rin);
     done |= 1u << i;
@@ -952,14 +932,10 @@ __device__ __forceinline__ uint32_t settled_run(const RoundParams& p, uint32_t l
 constexpr uint32_t kUniRun = 16;  // longest run settled_run_uni takes (p.tpw <= 16)
 
 // Everything settled_run_uni reads that depends on no other load (the run's A planes, the validity
-// word, the reference row's words, the Byzantine bits), requested at the start of the wave's run,
-// before the uniform test's slot words and the run's tile words are waited for: the settled wave
-// then waits for one memory latency instead of three in a row (slot words -> tile words -> A).
-// (A/B: requested at run start, before the uniform test, 4.24 vs 4.19-4.22 ms per C4 epoch after it,
-// profiles/r05/s14/ab_pre.log: the settled waves are not waiting on that chain; left off)
-#ifndef AVK_UNI_PREFETCH
-#define AVK_UNI_PREFETCH 0
-#endif
+// word, the reference row's words, the Byzantine bits), requested in two parts (uni_early,
+// uni_prefetch) once the run is known to take the uniform path. (Requested at the start of the wave's
+// run, before the uniform test, it measured no faster: 4.24 vs 4.19-4.22 ms per C4 epoch,
+// profiles/r05/s14/ab_pre.log: the settled waves are not waiting on that chain.)
 struct UniPre {
   uint32_t Av[kUniRun];
   uint32_t vw, refp, rin;
@@ -1041,16 +1017,9 @@ __device__ __forceinline__ uint32_t settled_run_uni(const RoundParams& p, uint32
     if ((m & (kPendAllLive | (kVMask << 8))) == (kPendAllLive | (kVUniform << 8))) cand |= 1u << i;
   }
   cand &= ~quiet;
-  uint32_t Av[kUniRun], Ov[kUniRun];
+  uint32_t Av[kUniRun];
 #pragma unroll
   for (uint32_t i = 0; i < kUniRun; ++i) Av[i] = u.Av[i];
-  // the overwritten published words (p.count_changed: publish) with them, not one dependent load per tile
-#pragma unroll
-  for (uint32_t i = 0; i < kUniRun; ++i) {
-    const uint32_t g = (t0 + i) * 64u + lane;
-    const uint32_t nl = (g < p.L ? g : p.L - 1u) >> p.bl_log2;
-    Ov[i] = AVK_CC_PREFETCH && CC && p.count_changed && ((cand >> i) & 1u) ? p.pref_out[(p.n0 + nl) * p.PS + b] : 0u;
-  }
   if constexpr (!CC) {
     // The single-GPU (non-counting) build walks the run with no per-tile branch: a tile is settled iff
     // it is a candidate and no polled record's A differs from the reference word (one ballot, a
@@ -1111,9 +1080,8 @@ __device__ __forceinline__ uint32_t settled_run_uni(const RoundParams& p, uint32
       // kpend >= 2: this settled tile's accepted plane is unchanged since the snapshot being
       // overwritten (publish): honest rows publish that word again, Byzantine rows its pattern's
       const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)meta, (int)i);
-      const bool known = AVK_CC_PREFETCH || (m & 0xFFu) >= 2u;
-      const uint32_t old = AVK_CC_PREFETCH ? Ov[i] : pub;
-      publish<POL, CC>(p, prow, pub, old, acc, known, nl, i);
+      const bool known = (m & 0xFFu) >= 2u;
+      publish<POL, CC>(p, prow, pub, pub, acc, known, nl, i);
     }
     done |= 1u << i;
     applied += 8u * (uint32_t)__popc(P0);
@@ -1348,26 +1316,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == kMo
           const uint32_t nlA = uni(div_bl(p, tile * 64u));
           const uint32_t nlB = uni(div_bl(p, min(tile_end * 64u, p.L) - 1u));
           const uint32_t nn = nlB - nlA + 1u;
-          // uniform rows: settled_run_uni's loads requested first (UniPre); wasted only in a klazy round
-          // whose input is not uniform (the converging rounds), where the general path re-reads A
+          // uniform rows: settled_run_uni's loads (UniPre)
           UniPre upre;
           const bool uni_ok = p.uni_in && p.lean && p.settled_fast && p.klazy && p.vv && nn <= 256u &&
                               tile_end - tile <= kUniRun;
-#if AVK_UNI_PREFETCH
-          if (uni_ok) {
-            uni_early(p, lane, nlA, upre);
-            (void)uni_prefetch<POL>(p, lane, tile, tile_end, nn, 0u, false, upre);
-          }
-#endif
           // the run's per-tile words, one lane per tile (tpw <= 16)
           const uint32_t ti = tile + lane;
           const uint32_t st = p.vv && ti < tile_end ? p.vstale[ti] : 0u;
           const uint32_t kw = (p.klazy || p.kconsume) && ti < tile_end ? p.kpend[ti] : 0u;
-#if !AVK_UNI_PREFETCH
           if constexpr (!CC) {  // (the counting build requests them where it always did, below)
             if (uni_ok) uni_early(p, lane, nlA, upre);
           }
-#endif
           wd.meta = (st << 8) | (kw & (kPendAllLive | kHiVirt | 0xFFu));
           wd.t0 = tile;
           wd.nlA = nlA;
@@ -1378,13 +1337,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == kMo
             // the run's quiescent tiles (above): settled candidates with two deferred rounds behind them,
             // both input snapshots uniform (a Byzantine node in the run: settled_run_uni drops them)
             const bool qt = !CC && prev_uni && p.quiet_tiles;
-#if !AVK_UNI_PREFETCH
             if constexpr (CC) uni_early(p, lane, nlA, upre);
             const uint32_t quiet = uni_prefetch<POL>(p, lane, tile, tile_end, nn, wd.meta, qt, upre);
-#else
-            const uint32_t quiet = 0u;
-            (void)qt;
-#endif
             uni_done = settled_run_uni<POL, CC>(p, lane, tile, tile_end, wd.meta, nlA, nn, upre, quiet, acc);
             uni_ran = true;
             // (a run holding a Byzantine node comes back with no tile done)
@@ -1640,9 +1594,6 @@ hipError_t launch_sweep_k(const RoundParams& p_in, SweepMode mode, uint32_t bloc
 // with non-temporal loads of its own), which also leaves L2 / MALL to the stale tiles' regathered
 // rows. A/B (tools/wb_probe.py, three alternations on one box, profiles/r05/s18/ab_matnt.log):
 // C4 0.80 -> 0.74 ms, C4p 0.65 -> 0.455, C5 1.56 -> 1.42 per segment end.
-#ifndef AVK_MAT_NT
-#define AVK_MAT_NT 1
-#endif
 // k_materialize writes back both deferred forms in one pass, before anything other than a warm k = 8
 // sim round reads or writes the records (do_v: stale vote planes, whose vote register is the last
 // round's 8 gathered votes, V_i = slot 7 - i, and unstored consider planes; do_k: pending count steps
@@ -1684,11 +1635,11 @@ __device__ __forceinline__ void materialize_tile(const RoundParams& p, uint32_t 
   // ---- stores
   if ((raw & kCAll) && x.active) {  // consider planes: all-ones
 #pragma unroll
-    for (int c = 0; c < 8; ++c) pst<AVK_MAT_NT>(tp + 1024u + (uint32_t)c * 64u + lane, ~0u);
+    for (int c = 0; c < 8; ++c) pst<true>(tp + 1024u + (uint32_t)c * 64u + lane, ~0u);
   }
   if (st && x.active) {
-    pst4<AVK_MAT_NT>(grp, o0);
-    pst4<AVK_MAT_NT>(grp + 64, o1);
+    pst4<true>(grp, o0);
+    pst4<true>(grp + 64, o1);
   }
   if (dok) {  // + 8 * pend on the polled records' counts
     uint32_t Kp[8];
@@ -1713,8 +1664,8 @@ __device__ __forceinline__ void materialize_tile(const RoundParams& p, uint32_t 
       o2[c] = Kp[c];
       o3[c] = Kp[4 + c];
     }
-    pst4<AVK_MAT_NT>(grp + 128, o2);
-    pst4<AVK_MAT_NT>(grp + 192, o3);
+    pst4<true>(grp + 128, o2);
+    pst4<true>(grp + 192, o3);
   }
 }
 

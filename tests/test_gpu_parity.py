@@ -319,9 +319,6 @@ def dense_words(k):  # kernels.h dense_words: u64 words of a dense lane record
     return (k + 5) // 2
 
 
-MED_MAX = 6  # kernels.h kMedMax (folded medium records, AVK_MED_S4 = 0 builds only)
-
-
 def emitted_bytes(u, k=8, med=False):
     """Log bytes the round kernels write for decoded updates `u`, per (round,
     node, 32-target block) with c updates. med=False (first-generation
@@ -373,7 +370,7 @@ def test_c4_shape_properties():
         assert e.applied_votes() == n * m * k * 16
         u = e.fetch_updates()
         r0 = u[:, 0] == 0
-        med = kernel == 2  # the sweep logs medium records (emit_updates_med)
+        med = kernel == 2  # the sweep logs medium records (emit_store_med)
         assert b1 == lanes * cold_bytes + emitted_bytes(u[r0], med=med)
         if warm_bytes is not None:
             assert b16 - b1 == lanes * warm_bytes + emitted_bytes(u[~r0], med=med)

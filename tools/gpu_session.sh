@@ -36,11 +36,9 @@ for s in "$@"; do
            step gm_um8 600 python tools/group_model.py --workload c4 --ranks 8 --kinds targets --target-option uni_merge=4 --json $OUT/group_model_c4_um8.json && \
            step gm_um8t16 600 python tools/group_model.py --workload c4 --ranks 8 --kinds targets --target-option tiles_per_wave=16 --json $OUT/group_model_c4_t16.json ;;
     wbprobe) step wbprobe 600 python tools/wb_probe.py --json $OUT/wb_probe.json ;;
-    ab_c2emit) step ab_c2emit 600 bash -c 'for i in 1 2 3; do for v in default late emit2 emit2late; do echo "== $v"; if [ $v = default ]; then python tools/fuse_probe.py | head -1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/fuse_probe.py | head -1; fi; done; done' ;;
     gm_t16) step gm_t16_c4 600 python tools/group_model.py --workload c4 --ranks 4,8 --kinds targets --target-option tiles_per_wave=16 --json $OUT/gm_t16_c4.json && \
             step gm_t16_c4p 600 python tools/group_model.py --workload c4p --ranks 4,8 --kinds targets --target-option tiles_per_wave=16 --json $OUT/gm_t16_c4p.json && \
             step gm_t16_c4pb 600 python tools/group_model.py --workload c4pb --ranks 4,8 --kinds targets --target-option tiles_per_wave=16 --json $OUT/gm_t16_c4pb.json ;;
-    ab_c2e) step ab_c2e 600 bash -c 'for i in 1 2 3; do for v in default emit2 late emit2late; do echo "== $v"; if [ $v = default ]; then python tools/fuse_probe.py --fuse 16 --repeat 15; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/fuse_probe.py --fuse 16 --repeat 15; fi; done; done' ;;
     ab_c5tpw) step ab_c5tpw 600 bash -c 'for i in 1 2; do for t in 8 16; do echo "== tpw $t"; python tools/round_probe.py --workload c5 --option tiles_per_wave=$t | tail -1; done; done' ;;
     gm_td) for w in c4 c4p c4pb; do
              step gm_td0_$w 600 python tools/group_model.py --workload $w --ranks 2,4,8 --kinds targets --target-option tile_draw=0 --json $OUT/gm_td0_$w.json || exit $?
@@ -48,18 +46,13 @@ for s in "$@"; do
            done ;;
     ab_c5td) step ab_c5td 600 bash -c 'for i in 1 2; do for o in "tile_draw=0" "tile_draw=1" "tile_draw=1 --option tiles_per_wave=16"; do echo "== $o"; python tools/round_probe.py --workload c5 --option $o | tail -1; done; done' ;;
     teststd) step pytest_td 600 python -u -m pytest tests/test_gpu_parity.py -k "target_shard" tests/test_gpu_uniform_rows.py tests/test_gpu_log_layout.py -x -v -p no:cacheprovider --timeout 300 --timeout-method thread ;;
-    ab_c2b) step ab_c2b 600 bash -c 'for i in 1 2 3; do for v in default buf3 buf3chk emit1; do echo "== $v"; if [ $v = default ]; then python tools/fuse_probe.py --fuse 16 --repeat 15; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/fuse_probe.py --fuse 16 --repeat 15; fi; done; done' ;;
     testsrep) step pytest_rep 600 python -u -m pytest tests/test_gpu_replay_fused.py tests/test_gpu_parity.py -k "replay or target_shard or capped" -x -v -p no:cacheprovider --timeout 300 --timeout-method thread ;;
-    ab_pre) step ab_pre 600 bash -c 'for i in 1 2 3; do for v in default nopre; do echo "== $v"; if [ $v = default ]; then python tools/round_probe.py --workload c4 | tail -1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload c4 | tail -1; fi; done; done' ;;
     ab_unc) step ab_unc 900 bash -c 'for w in c5 c4 c4p; do for i in 1 2; do for o in 0 1; do echo "== $w pref_uncached=$o"; python tools/round_probe.py --workload $w --option pref_uncached=$o | tail -1; done; done; done' ;;
-    ab_c2p) step ab_c2p 600 bash -c 'for i in 1 2 3; do for v in default pipe3 pipe3late; do echo "== $v"; if [ $v = default ]; then python tools/fuse_probe.py --fuse 16 --repeat 15; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/fuse_probe.py --fuse 16 --repeat 15; fi; done; done' ;;
-    testsrepv) step pytest_repv 600 env AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_${V:-pipe3}.so python -u -m pytest tests/test_gpu_replay_fused.py -x -q -p no:cacheprovider --timeout 300 --timeout-method thread ;;
     c2pmc) step c2pmc 300 timeout -s KILL 240 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_IFETCH SQ_INSTS_VALU GRBM_GUI_ACTIVE \
             --output-format csv -d $OUT/c2pmc -o c2 -- python3 tools/fuse_probe.py --fuse 16 --repeat 3 ;;
     gm_ptpw) step gm_ptpw_c4p 600 python tools/group_model.py --workload c4p --ranks 4,8 --kinds masked --variant tpw8:tiles_per_wave=8 --variant tpw4:tiles_per_wave=4 --json $OUT/gm_ptpw_c4p.json && \
              step gm_ptpw_c4pb 600 python tools/group_model.py --workload c4pb --ranks 4,8 --kinds masked --variant tpw8:tiles_per_wave=8 --variant tpw4:tiles_per_wave=4 --json $OUT/gm_ptpw_c4pb.json ;;
     c2abl) step c2abl 300 bash -c 'for i in 1 2; do for o in "replay_fast=1" "ablate_emit=1"; do echo "== $o"; python tools/fuse_probe.py --fuse 16 --repeat 15 --option $o; done; done' ;;
-    ab_matnt) step ab_matnt 600 bash -c 'for i in 1 2 3; do for v in default matnt; do echo "== $v"; if [ $v = default ]; then python tools/wb_probe.py --runs 1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/wb_probe.py --runs 1; fi; done; done' ;;
     probes) step probes 600 bash -c 'for w in c4 c4 c5 c4p; do echo "== $w"; python tools/round_probe.py --workload $w | tail -17; done' ;;
     benchx2) step bench_a 900 python bench.py --full && step bench_b 900 python bench.py --full ;;
     profc4) step profc4 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/profc4 -o c4 -- \
@@ -69,7 +62,6 @@ for s in "$@"; do
     gm_c4) step gm_c4 900 python tools/group_model.py --workload c4 --variant nomask:peer_mask=0 --variant tpw16:tiles_per_wave=16 --variant nomask_tpw16:peer_mask=0,tiles_per_wave=16 --json $OUT/group_model_c4.json ;;
     gm_c4p) step gm_c4p 900 python tools/group_model.py --workload c4p --variant nomask:peer_mask=0 --json $OUT/group_model_c4p.json ;;
     gm_c4pb) step gm_c4pb 900 python tools/group_model.py --workload c4pb --variant nomask:peer_mask=0 --json $OUT/group_model_c4pb.json ;;
-    ab_c2late) step ab_c2late 600 bash -c 'for i in 1 2 3; do for v in default late; do echo "== $v"; if [ $v = default ]; then python tools/fuse_probe.py | head -1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_late.so python tools/fuse_probe.py | head -1; fi; done; done' ;;
     gm_ab) step gm_ab 900 python tools/group_model.py --workload c4p --ranks 8 --kinds targets,masked --variant scoped:push_store=0 --variant ablate:push_store=2 --variant direct:push_defer=0 --variant nomask_abl:peer_mask=0,push_store=2 --variant nomask:peer_mask=0 --json $OUT/group_model_c4p_ab.json ;;
     gm_trace) step gm_trace 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/gm_trace -o gm -- \
             python3 tools/group_model.py --workload c4p --ranks 8 --kinds masked --json $OUT/gm_trace.json ;;
@@ -221,7 +213,6 @@ for s in "$@"; do
              step gm_cold_c4p 900 python tools/group_model.py --workload c4p --ranks 8 --kinds targets,masked --json $OUT/gm_cold_c4p.json && \
              step gm_warm_c4 900 python tools/group_model.py --workload c4 --ranks 8 --kinds targets,masked --all-option warm_pref=1 --json $OUT/gm_warm_c4.json ;;
     smaxtests) step smaxtests 900 python -u -m pytest tests/test_gpu_compact.py tests/test_gpu_delivery.py tests/test_gpu_log_layout.py tests/test_gpu_parity.py tests/test_gpu_fullsize.py -x -q -p no:cacheprovider --timeout 300 --timeout-method thread ;;
-    ab_smax) step ab_smax 900 bash -c 'for i in 1 2; do for w in c4p c4 c4pb; do for v in default smax1; do echo "== $w $v"; if [ $v = default ]; then python tools/round_probe.py --workload $w --rounds 8 | tail -1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w --rounds 8 | tail -1; fi; done; done; done' ;;
     ab_wd) step ab_wd 900 bash -c 'for i in 1 2; do for w in c4p c4; do for o in "wave_dense=0" "wave_dense=32" "wave_dense=1"; do echo "== $w $o"; python tools/round_probe.py --workload $w --rounds 6 --option $o | tail -7; done; done; done' ;;
     wdtests) step wdtests 600 env AVHIP_TEST_OPTIONS=wave_dense=1 python -u -m pytest tests/test_gpu_compact.py -x -q -p no:cacheprovider --timeout 300 --timeout-method thread ;;
     ab_uv) step ab_uv 900 bash -c 'for i in 1 2; do for w in c4 c5; do for o in "uni_votes=1" "uni_votes=0"; do echo "== $w $o"; python tools/round_probe.py --workload $w --rounds 10 --option $o | tail -11; done; done; done' ;;
@@ -233,39 +224,22 @@ for s in "$@"; do
     self2s) step self2s 900 python bench.py --full --gpus 2 --rehearse-one-gpu --detail $OUT/rehearse2s_detail.json ;;
     exchcost) step exchcost 300 python tools/exchange_cost.py --json gpurun_out/exchange_cost.json ;;
     barrier4) step barrier4 400 bash -c 'python tools/barrier_cost.py --world 2 --json gpurun_out/barrier2_small.json && python tools/barrier_cost.py --world 2 --nodes 131072 --json gpurun_out/barrier2_big.json && python tools/barrier_cost.py --world 4 --nodes 131072 --json gpurun_out/barrier4_big.json && python tools/barrier_cost.py --world 2 --nodes 1000000 --rounds 40 --json gpurun_out/barrier2_c4.json' ;;
-    abr3) step abr3 600 bash -c 'for w in c4 c4p c4pb; do for v in new nohoist r3; do echo "== $w $v"; if [ $v = new ]; then python tools/round_probe.py --workload $w | tail -1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w | tail -1; fi; done; done; for v in new r3; do echo "== c2 $v"; if [ $v = new ]; then python tools/fuse_probe.py; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/fuse_probe.py; fi; done' ;;
     ablate) step ablate 600 bash -c 'for w in c4 c4p; do for o in "ablate_phase=0" "ablate_phase=1" "ablate_phase=2" "ablate_phase=4" "ablate_phase=16" "ablate_emit=1" "ablate_phase=7 --option ablate_emit=1"; do echo "== $w $o"; AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_ablate.so python tools/round_probe.py --workload $w --rounds 8 --option $o | grep -v "^{\"workload"; done; done' ;;
     quick) step quick 900 python -u -m pytest tests/test_gpu_peer_push.py tests/test_gpu_parity.py tests/test_gpu_uniform_rows.py tests/test_gpu_count_lazy.py tests/test_gpu_virtual_votes.py tests/test_gpu_fresh.py tests/test_gpu_replay_fused.py -x -q -p no:cacheprovider --timeout 300 --timeout-method thread ;;
     tshard) step tshard 600 bash -c 'for o in tiles_per_wave=4 tiles_per_wave=8 tiles_per_wave=16; do python tools/shard_model.py --workload c4 --kinds targets --no-one-gpu --ranks 2,4,8 --option $o --json gpurun_out/tshard_c4_$o.json | tail -3; done' ;;
     shardmodel2) step shardmodel2 600 bash -c 'python tools/shard_model.py --workload c4 --json gpurun_out/shard_model_c4.json && python tools/shard_model.py --workload c4p --json gpurun_out/shard_model_c4p.json && python tools/shard_model.py --workload c4pb --json gpurun_out/shard_model_c4pb.json' ;;
-    abuni4) step abuni4 600 bash -c 'for w in c4 c5 c4pb; do for v in new s3; do echo "== $w $v"; if [ $v = new ]; then python tools/round_probe.py --workload $w; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w; fi; done; done' ;;
-    abdense) step abdense 600 bash -c 'for w in c4 c4p c4pb; do for v in new dense2 dense4; do echo "== $w $v"; if [ $v = new ]; then python tools/round_probe.py --workload $w | tail -1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w | tail -1; fi; done; done' ;;
-    abs4) step abs4 900 bash -c 'for w in c4 c4p c4pb; do for v in new walk walk0; do echo "== $w $v"; if [ $v = new ]; then python tools/round_probe.py --workload $w; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w; fi; done; done; for v in new walk0; do echo "== c2 $v"; if [ $v = new ]; then python tools/fuse_probe.py; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/fuse_probe.py; fi; done' ;;
     tsparity) step tsparity 600 python -u -m pytest tests/test_gpu_parity.py -x -v -p no:cacheprovider --timeout 300 --timeout-method thread -k "target_shard" ;;
     abemit) step abemit 600 bash -c 'for w in c4p c4; do for o in 0 1 2 3; do echo "== $w ablate_emit=$o"; python tools/round_probe.py --workload $w --option ablate_emit=$o | tail -1; done; done' ;;
     ablate5) step ablate5 600 bash -c 'for w in c4p; do for o in "ablate_phase=0" "ablate_phase=1" "ablate_phase=2" "ablate_phase=4" "ablate_phase=16" "ablate_emit=1" "ablate_phase=7 --option ablate_emit=1"; do echo "== $w $o"; AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_ablate.so python tools/round_probe.py --workload $w --rounds 8 --option $o | grep -v "^{\"workload"; done; done' ;;
     tshard2) step tshard2 600 python tools/shard_model.py --workload c4 --kinds targets --ranks 2,4,8 --json gpurun_out/tshard_c4_default.json ;;
-    c2x) step c2x 600 bash -c 'AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_c2x.so python -u -m pytest tests/test_gpu_replay_fused.py tests/test_gpu_parity.py -x -q -p no:cacheprovider --timeout 300 --timeout-method thread -k "replay or c2 or capped or fused" && for v in new c2x new c2x; do echo "== c2 $v"; if [ $v = new ]; then python tools/fuse_probe.py; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/fuse_probe.py; fi; done' ;;
     full4p) step full4p 900 python -u -m pytest tests/test_gpu_fullsize.py tests/test_gpu_bench_protocol.py -x -v -p no:cacheprovider --timeout 600 --timeout-method thread ;;
-    abs5) step abs5 900 bash -c 'for w in c4 c4p c4pb; do for v in new walk0; do echo "== $w $v"; if [ $v = new ]; then python tools/round_probe.py --workload $w; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w; fi; done; done; for v in new walk0 new walk0; do echo "== c2 $v"; if [ $v = new ]; then python tools/fuse_probe.py; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/fuse_probe.py; fi; done' ;;
-    abpad) step abpad 900 bash -c 'for w in c4p c4 c4pb c4p; do for v in new pad; do echo "== $w $v"; if [ $v = new ]; then python tools/round_probe.py --workload $w | tail -1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w | tail -1; fi; done; done; for o in 2 3; do echo "== c4p pad ablate_emit=$o"; AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_pad.so python tools/round_probe.py --workload c4p --option ablate_emit=$o | tail -1; done; for v in new pad; do echo "== c2 $v"; if [ $v = new ]; then python tools/fuse_probe.py; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/fuse_probe.py; fi; done' ;;
-    quicktwo) step quicktwo 900 env AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_two.so python -u -m pytest tests/test_gpu_peer_push.py tests/test_gpu_parity.py tests/test_gpu_uniform_rows.py tests/test_gpu_count_lazy.py tests/test_gpu_virtual_votes.py tests/test_gpu_fresh.py tests/test_gpu_replay_fused.py -x -q -p no:cacheprovider --timeout 300 --timeout-method thread ;;
-    abtwo) step abtwo 900 bash -c 'for w in c4p c4pb c4 c4p; do for v in pad two; do echo "== $w $v"; AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w | tail -1; done; done; for v in pad two; do echo "== c2 $v"; AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/fuse_probe.py; done' ;;
     profc4) step profc4 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/profc4 -o c4 -- python3 bench.py --full --no-cpu-baseline --no-secondary ;;
-    ablognt) step ablognt 600 bash -c 'for w in c4p c4 c4pb c4p; do for v in new lognt; do echo "== $w $v"; if [ $v = new ]; then python tools/round_probe.py --workload $w | tail -1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w | tail -1; fi; done; done' ;;
-    abpub) step abpub 600 bash -c 'for w in c4p c4 c4pb c4p; do for v in new pubplain sp3; do echo "== $w $v"; if [ $v = new ]; then python tools/round_probe.py --workload $w | tail -1; elif [ $v = sp3 ]; then python tools/round_probe.py --workload $w --option store_policy=3 | tail -1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w | tail -1; fi; done; done' ;;
-    abwpe) step abwpe 600 bash -c 'for w in c4p c4 c4pb c4p c4; do for v in new w5 w7; do echo "== $w $v"; if [ $v = new ]; then python tools/round_probe.py --workload $w | tail -1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w | tail -1; fi; done; done' ;;
-    abwpe2) step abwpe2 600 bash -c 'for w in c4p c4 c4pb c4p c4 c5 c3; do for v in new w5 w4; do echo "== $w $v"; if [ $v = new ]; then python tools/round_probe.py --workload $w | tail -1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w | tail -1; fi; done; done' ;;
-    abf5) step abf5 600 bash -c 'for w in c4 c4p c4 c4p c4pb c5; do for v in w5 f5; do echo "== $w $v"; AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w > gpurun_out/rp_tmp.txt 2>/dev/null; head -1 gpurun_out/rp_tmp.txt; tail -1 gpurun_out/rp_tmp.txt; done; done' ;;
     self4s) step self4s 900 python bench.py --full --gpus 4 --rehearse-one-gpu --detail $OUT/rehearse4s_detail.json ;;
     abrun8) step abrun8 600 bash -c 'for w in c4 c4p c4 c4p c4pb; do for o in "tiles_per_wave=0 --option uni_merge=1" "tiles_per_wave=8 --option uni_merge=2" "tiles_per_wave=4 --option uni_merge=4"; do echo "== $w $o"; python tools/round_probe.py --workload $w --option $o | tail -1; done; done' ;;
     abc5tpw) step abc5tpw 600 bash -c 'for w in c5 c5; do for o in 0 4 16; do echo "== $w tpw=$o"; python tools/round_probe.py --workload $w --option tiles_per_wave=$o | tail -1; done; done' ;;
-    c2ab) step c2ab 300 bash -c 'for v in new s3; do echo "== c2 $v"; if [ $v = new ]; then python tools/fuse_probe.py; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/fuse_probe.py; fi; done' ;;
     reh2pb) step reh2pb 600 python bench.py --full --gpus 2 --rehearse-one-gpu --workload c4pb --shard peers --no-secondary --detail $OUT/rehearse2_c4pb_detail.json ;;
     reh2t) step reh2t 600 python bench.py --full --gpus 2 --rehearse-one-gpu --shard targets --no-secondary --detail $OUT/rehearse2_targets_detail.json ;;
-    abs3) step abs3 900 bash -c 'for w in c4 c4p c4pb c3; do for v in new s3; do for cc in 0 1; do echo "== $w $v count_changed=$cc"; if [ $v = new ]; then python tools/round_probe.py --workload $w --option count_changed=$cc | tail -1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w --option count_changed=$cc | tail -1; fi; done; done; done; for v in new s3; do echo "== c2 $v"; if [ $v = new ]; then python tools/fuse_probe.py; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/fuse_probe.py; fi; done' ;;
     profc2b) step profc2b 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/profc2b -o c2 -- python3 bench.py --full --workload c2 --no-cpu-baseline --no-secondary ;;
-    abcc) step abcc 600 bash -c 'for w in c4 c4p; do for v in new noccpf; do for cc in 0 1; do echo "== $w $v count_changed=$cc"; if [ $v = new ]; then python tools/round_probe.py --workload $w --option count_changed=$cc | tail -1; else AVHIP_LIB=go-avalanche_amd/lib/variants/libavhip_$v.so python tools/round_probe.py --workload $w --option count_changed=$cc | tail -1; fi; done; done; done; python tools/round_probe.py --workload c4pb | tail -1' ;;
     shardmodel) step shardmodel 600 bash -c 'python tools/shard_model.py --workload c4 --json gpurun_out/shard_model_c4.json && python tools/shard_model.py --workload c4p --json gpurun_out/shard_model_c4p.json' ;;
     fused4) step fused4 600 python -u -m pytest tests/test_gpu_replay_fused.py tests/test_gpu_parity.py -x -v -p no:cacheprovider --timeout 300 --timeout-method thread ;;
     peer4) step peer4 600 python -u -m pytest tests/test_gpu_peer_push.py -x -v -p no:cacheprovider --timeout 120 --timeout-method thread ;;
