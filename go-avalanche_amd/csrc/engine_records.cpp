@@ -1,0 +1,565 @@
+// libavhip.so: record I/O outside a round. Validity and added targets, the drop-in vote batches,
+// reads and writes of records, preferences and poll sets, the census and the counter queries.
+#include <cstring>
+
+#include "engine.h"
+
+using namespace aveng;
+
+namespace {
+
+// Peer-push engines keep every replica of a snapshot buffer identical; a
+// write to this rank's rows outside a round would break that.
+int peer_local_write_check(const av_engine* e) {
+  AV_CHECK(e->peer_world <= 1, AV_ERR_UNSUPPORTED,
+           "record writes outside a round are not supported on a peer-push node-sharded engine");
+  return AV_OK;
+}
+
+// A sharded 64-bit device counter (kLogShards words at dev) copied back and added up.
+int sum_shards(av_engine* e, const unsigned long long* dev, int64_t* out) {
+  std::vector<unsigned long long> c(avk::kLogShards);
+  AV_HIP(hipMemcpyAsync(c.data(), dev, avk::kLogShards * 8, hipMemcpyDeviceToHost, e->stream));
+  AV_HIP(hipStreamSynchronize(e->stream));
+  unsigned long long t = 0;
+  for (auto v : c) t += v;
+  *out = (int64_t)t;
+  return AV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int av_set_valid(av_engine* e, int64_t target, int32_t valid) {
+  if (e) e->facts.snapshot_written();
+  AV_ENTER(e);
+  AV_CHECK(target >= 0 && target < e->M, AV_ERR_INVALID_ARG, "target out of range");
+  if (!local_target(e, target)) return AV_OK;
+  AV_TRY(materialize_votes(e));  // stale tiles must not gain live-but-invalid records
+  const int64_t tl = target - e->t0;
+  const uint32_t b = (uint32_t)(tl >> 5), m = 1u << (tl & 31);
+  e->valid_host[b] = valid ? (e->valid_host[b] | m) : (e->valid_host[b] & ~m);
+  AV_HIP(hipMemcpyAsync(e->valid + b, &e->valid_host[b], 4, hipMemcpyHostToDevice, e->stream));
+  AV_HIP(hipStreamSynchronize(e->stream));
+  return AV_OK;
+}
+
+int av_add_targets(av_engine* e, int64_t node, const int64_t* targets, const uint8_t* accepted, int64_t n,
+                   uint8_t* added) {
+  if (e) e->facts.snapshot_written();
+  AV_ENTER(e);
+  AV_TRY(peer_local_write_check(e));
+  AV_CHECK(n >= 0 && (n == 0 || (targets && accepted && added)), AV_ERR_INVALID_ARG, "null argument");
+  AV_CHECK(local_node(e, node), AV_ERR_INVALID_ARG, "node %lld not in this shard", (long long)node);
+  AV_TRY(materialize_votes(e));
+  e->facts.add_targets();
+  std::vector<uint32_t> tl;
+  std::vector<uint8_t> acc;
+  std::vector<int64_t> pos;
+  for (int64_t i = 0; i < n; ++i) {
+    added[i] = 0;
+    if (!local_target(e, targets[i])) continue;
+    tl.push_back((uint32_t)(targets[i] - e->t0));
+    acc.push_back(accepted[i] ? 1 : 0);
+    pos.push_back(i);
+  }
+  if (tl.empty()) return AV_OK;
+  const size_t m = tl.size();
+  avmem::DevBuf<void> s;
+  AV_HIP(s.alloc(m * 6 + 64));
+  auto* dt = static_cast<uint32_t*>(s.get());
+  auto* da = reinterpret_cast<uint8_t*>(dt + m);
+  auto* dadd = da + m;
+  AV_HIP(hipMemcpyAsync(dt, tl.data(), m * 4, hipMemcpyHostToDevice, e->stream));
+  AV_HIP(hipMemcpyAsync(da, acc.data(), m, hipMemcpyHostToDevice, e->stream));
+  avk::AddParams p{};
+  p.planes = e->planes;
+  p.pref = e->pref[e->cur];
+  p.valid = e->valid;
+  p.byz = e->byz;
+  p.targets = dt;
+  p.accepted = da;
+  p.added = dadd;
+  p.n = (uint32_t)m;
+  p.node_local = (uint32_t)(node - e->n0);
+  p.node = (uint32_t)node;
+  p.BL = e->BL;
+  p.PS = e->PS;
+  p.round = (uint32_t)e->round;
+  p.pub_mode = (uint32_t)e->pub_mode;
+  AV_HIP(avk::launch_add_targets(p, e->stream));
+  std::vector<uint8_t> res(m);
+  AV_HIP(hipMemcpyAsync(res.data(), dadd, m, hipMemcpyDeviceToHost, e->stream));
+  AV_HIP(hipStreamSynchronize(e->stream));
+  for (size_t i = 0; i < m; ++i) added[pos[i]] = res[i];
+  return AV_OK;
+}
+
+int av_register_votes(av_engine* e, int64_t node, const int64_t* targets, const uint32_t* errs, int64_t n,
+                      int32_t* status_out) {
+  const int64_t offs[2] = {0, n};
+  return av_register_votes_batch(e, 1, &node, offs, targets, errs, status_out);
+}
+
+// Many Responses in one call (processor.go:61-122 for each, in order). The
+// host packs each vote into one u32 (target's local index, unknown-hash, yes
+// and considered bits: dropin_word) in pinned memory, in parallel, and checks
+// on the way whether every Response has strictly ascending targets (a poll
+// set's order, rule R1). Then:
+//  * fast path (it holds): one workgroup per node applies the node's
+//    Responses in call order, each lane's run of votes where it lies
+//    (k_dropin_resp), no grouping step;
+//  * otherwise: lane keys on the device, the hand-written stable radix sort
+//    of (lane, vote position) and run-length encoding (log_ops.hip
+//    launch_group_votes, dev_scan.h), then
+//    k_register_votes over the runs.
+// Statuses come back as one byte per vote and are widened on the host.
+// Copies: 4 B per vote each way plus 1 B back (the caller's int64 hashes and
+// u32 errs are never copied as such).
+int av_register_votes_batch(av_engine* e, int64_t n_resp, const int64_t* nodes, const int64_t* offsets,
+                            const int64_t* targets, const uint32_t* errs, int32_t* status_out) {
+  if (e) e->facts.snapshot_written();
+  AV_ENTER(e);
+  AV_TRY(peer_local_write_check(e));
+  AV_CHECK(n_resp >= 0 && (n_resp == 0 || (nodes && offsets)), AV_ERR_INVALID_ARG, "null argument");
+  if (n_resp == 0) return AV_OK;
+  AV_CHECK(n_resp < (1ll << 31), AV_ERR_INVALID_ARG, "too many Responses in one call");
+  AV_CHECK(offsets[0] == 0, AV_ERR_INVALID_ARG, "offsets[0] must be 0");
+  for (int64_t i = 0; i < n_resp; ++i) {
+    AV_CHECK(offsets[i + 1] >= offsets[i], AV_ERR_INVALID_ARG, "offsets must not decrease");
+    AV_CHECK(local_node(e, nodes[i]), AV_ERR_INVALID_ARG, "node %lld not in this shard", (long long)nodes[i]);
+  }
+  const int64_t n = offsets[n_resp];
+  AV_CHECK(n == 0 || (targets && errs && status_out), AV_ERR_INVALID_ARG, "null argument");
+  AV_CHECK(n < (1ll << 31), AV_ERR_INVALID_ARG, "too many votes in one call");
+  AV_CHECK(e->t1 - e->t0 <= (int64_t)avk::kDropTl + 1, AV_ERR_UNSUPPORTED, "drop-in votes need <= 4M local targets");
+  AV_TRY(materialize_votes(e));
+  // at most one confidence step per vote: bound by the most votes one node gets; the Responses
+  // grouped by node, in call order inside a group (fast path)
+  int64_t max_node_votes = 0;
+  std::vector<uint32_t> order((size_t)n_resp), grp_off;
+  {
+    std::vector<std::pair<int64_t, uint32_t>> nn((size_t)n_resp);
+    for (int64_t i = 0; i < n_resp; ++i) nn[(size_t)i] = {nodes[i], (uint32_t)i};
+    std::sort(nn.begin(), nn.end());  // (node, Response index): call order inside a node
+    for (size_t i = 0; i < nn.size();) {
+      int64_t c = 0;
+      size_t j = i;
+      grp_off.push_back((uint32_t)i);
+      for (; j < nn.size() && nn[j].first == nn[i].first; ++j) {
+        c += offsets[nn[j].second + 1] - offsets[nn[j].second];
+        order[j] = nn[j].second;
+      }
+      max_node_votes = std::max(max_node_votes, c);
+      i = j;
+    }
+    grp_off.push_back((uint32_t)n_resp);
+  }
+  const uint32_t n_groups = (uint32_t)grp_off.size() - 1u;
+  if (n == 0) {
+    e->facts.dropin_votes(max_node_votes, false);
+    return AV_OK;
+  }
+  // ---- pack (pinned): votes, then the Response table
+  const size_t tab_words = 2 * (size_t)n_resp + 1 + (size_t)n_resp + n_groups + 1;  // off, node, order, grp_off
+  const size_t hb = (size_t)n * 5 + tab_words * 4 + 64;
+  // (pinned host staging, grown on demand and kept by the engine)
+  AV_HIP(e->dropin_host.reserve(hb, avmem::Slack::kMiB, hipHostMallocDefault));
+  auto* hpack = static_cast<uint32_t*>(e->dropin_host.get());
+  auto* hoff = hpack + n;
+  auto* hnode = hoff + n_resp + 1;
+  auto* horder = hnode + n_resp;
+  auto* hgrp = horder + n_resp;
+  auto* hstat = reinterpret_cast<int8_t*>(hgrp + n_groups + 1);
+  for (int64_t i = 0; i <= n_resp; ++i) hoff[i] = (uint32_t)offsets[i];
+  for (int64_t i = 0; i < n_resp; ++i) hnode[i] = (uint32_t)(nodes[i] - e->n0);
+  std::memcpy(horder, order.data(), (size_t)n_resp * 4);
+  std::memcpy(hgrp, grp_off.data(), ((size_t)n_groups + 1) * 4);
+  std::vector<uint8_t> asc_t(64, 1), neutral_t(64, 0);
+  const int64_t T0 = e->t0, T1 = e->t1;
+  parallel_chunks(n_resp, std::max<int64_t>(1, n_resp * (1 << 18) / std::max<int64_t>(1, n)),
+                  [&](int t, int64_t r0, int64_t r1) {
+    bool asc = true, neutral = false;
+    for (int64_t r = r0; r < r1; ++r) {
+      for (int64_t v = offsets[r]; v < offsets[r + 1]; ++v) {
+        const int64_t tg = targets[v];
+        const uint32_t err = errs[v];
+        hpack[v] = avk::dropin_word(tg - T0, tg >= T0 && tg < T1, err);
+        neutral |= (int32_t)err < 0;
+        if (v > offsets[r]) asc &= tg > targets[v - 1];
+      }
+    }
+    asc_t[t] = asc;
+    neutral_t[t] = neutral;
+  });
+  bool ascending = true, neutral = false;
+  for (int t = 0; t < 64; ++t) {
+    ascending &= asc_t[t] != 0;
+    neutral |= neutral_t[t] != 0;
+  }
+  e->facts.dropin_votes(max_node_votes, neutral);
+  const bool fast = ascending && e->dropin_fast;
+  // ---- device: packed votes + Response table + byte statuses (+ grouping scratch)
+  size_t tb = 0;
+  int key_bits = 1;
+  const uint32_t m = (uint32_t)n;
+  if (!fast) {
+    const uint64_t keys_total = (uint64_t)e->L + 1;  // L = unknown targets
+    while (key_bits < 32 && (1ull << key_bits) < keys_total) ++key_bits;
+    tb = (size_t)avk::group_votes_scratch_words(m) * 8;
+  }
+  // packed | off | node | status bytes || keys vidx info keys_s perm_s keys_t perm_t lanes offs(m+1) nruns
+  // entries(2m) | u64 scratch (radix sort, run scan)
+  const size_t head_words = (size_t)m + tab_words + ((size_t)m + 3) / 4;
+  const size_t grp_words = fast ? 0 : 8 * (size_t)m + ((size_t)m + 1) + 1 + 2 * (size_t)m;
+  void* buf = nullptr;
+  AV_TRY(engine_scratch(e, (head_words + grp_words) * 4 + tb + 512, &buf));
+  auto* w = static_cast<uint32_t*>(buf);
+  uint32_t *dpack = w, *doff = dpack + m, *dnode = doff + n_resp + 1, *dorder = dnode + n_resp,
+           *dgrp = dorder + n_resp;
+  auto* dstat = reinterpret_cast<int8_t*>(dgrp + n_groups + 1);
+  AV_HIP(hipMemcpyAsync(dpack, hpack, ((size_t)m + tab_words) * 4, hipMemcpyHostToDevice, e->stream));
+  AV_HIP(hipMemsetAsync(dstat, 0xFF, (size_t)m, e->stream));
+  avk::DropInParams p{};
+  p.planes = e->planes;
+  p.pref = e->pref[e->cur];
+  p.valid = e->valid;
+  p.byz = e->byz;
+  p.status_out = dstat;
+  p.n0 = (uint32_t)e->n0;
+  p.BL = e->BL;
+  p.PS = e->PS;
+  p.L = e->L;
+  p.round = (uint32_t)e->round;
+  p.pub_mode = (uint32_t)e->pub_mode;
+  p.packed = dpack;
+  p.resp_off = doff;
+  p.resp_node = dnode;
+  p.n_resp = (uint32_t)n_resp;
+  p.order = dorder;
+  p.grp_off = dgrp;
+  p.n_groups = n_groups;
+  if (fast) {
+    AV_HIP(avk::launch_dropin_resp(p, e->stream));
+  } else {
+    uint32_t* g0 = w + head_words;
+    uint32_t *keys = g0, *vidx = keys + m, *info = vidx + m, *keys_s = info + m, *perm_s = keys_s + m,
+             *keys_t = perm_s + m, *perm_t = keys_t + m, *lanes = perm_t + m, *offs = lanes + m,
+             *nruns = offs + m + 1, *ent = nruns + 1;
+    auto* temp = reinterpret_cast<uint64_t*>(((uintptr_t)(ent + 2 * (size_t)m) + 255) & ~(uintptr_t)255);
+    AV_HIP(avk::launch_dropin_keys(p, keys, vidx, info, e->stream));
+    AV_HIP(avk::launch_group_votes(temp, keys, vidx, info, m, key_bits, keys_s, perm_s, keys_t, perm_t, lanes, offs,
+                                   nruns, ent, e->stream));
+    uint32_t nb = 0;
+    AV_HIP(hipMemcpyAsync(&nb, nruns, 4, hipMemcpyDeviceToHost, e->stream));
+    AV_HIP(hipStreamSynchronize(e->stream));
+    p.blocks = lanes;
+    p.offs = offs;
+    p.entries = ent;
+    p.n_blocks = nb;
+    AV_HIP(avk::launch_register_votes(p, e->stream));
+  }
+  AV_HIP(hipMemcpyAsync(hstat, dstat, (size_t)m, hipMemcpyDeviceToHost, e->stream));
+  AV_HIP(hipStreamSynchronize(e->stream));
+  parallel_chunks(n, 1 << 20, [&](int, int64_t a, int64_t b) {
+    for (int64_t i = a; i < b; ++i) status_out[i] = hstat[i];
+  });
+  return AV_OK;
+}
+
+int av_read_records(av_engine* e, int64_t n0, int64_t n1, int64_t t0, int64_t t1, uint32_t* out) {
+  AV_ENTER(e);
+  AV_PEER_SYNC_CHECK(e);
+  AV_CHECK(out && n0 >= e->n0 && n0 <= n1 && n1 <= e->n1 && t0 >= e->t0 && t0 <= t1 && t1 <= e->t1,
+           AV_ERR_INVALID_ARG, "range outside this engine's shard");
+  const size_t n = (size_t)(n1 - n0) * (size_t)(t1 - t0);
+  if (!n) return AV_OK;
+  // the deferred forms (stale vote planes, pending count steps) are read
+  // through, not written back: a read leaves the next round's fast paths on
+  avk::RoundParams p = round_params(e, nullptr);
+  p.vv = e->facts.v_stale ? 1u : 0u;
+  p.klazy = e->facts.k_pend ? 1u : 0u;
+  void* buf = nullptr;
+  AV_TRY(engine_scratch(e, n * 4, &buf));
+  AV_HIP(avk::launch_read_records_virtual(p, (uint32_t)(n0 - e->n0), (uint32_t)(n1 - e->n0), (uint32_t)(t0 - e->t0),
+                                          (uint32_t)(t1 - e->t0), static_cast<uint32_t*>(buf), e->stream));
+  AV_HIP(hipMemcpyAsync(out, buf, n * 4, hipMemcpyDeviceToHost, e->stream));
+  AV_HIP(hipStreamSynchronize(e->stream));
+  AV_PEER_CHECK(e);
+  return AV_OK;
+}
+
+int av_write_records(av_engine* e, int64_t n0, int64_t n1, int64_t t0, int64_t t1, const uint32_t* in) {
+  if (e) e->facts.snapshot_written();
+  AV_ENTER(e);
+  AV_TRY(peer_local_write_check(e));
+  AV_CHECK(in && n0 >= e->n0 && n0 <= n1 && n1 <= e->n1 && t0 >= e->t0 && t0 <= t1 && t1 <= e->t1,
+           AV_ERR_INVALID_ARG, "range outside this engine's shard");
+  AV_TRY(materialize_votes(e));
+  const size_t n = (size_t)(n1 - n0) * (size_t)(t1 - t0);
+  if (!n) return AV_OK;
+  e->facts.write_records();
+  avmem::DevBuf<uint32_t> s;
+  AV_HIP(s.alloc(n));
+  AV_HIP(hipMemcpyAsync(s, in, n * 4, hipMemcpyHostToDevice, e->stream));
+  AV_HIP(avk::launch_write_records(e->planes, e->BL, (uint32_t)(n0 - e->n0), (uint32_t)(n1 - e->n0),
+                                   (uint32_t)(t0 - e->t0), (uint32_t)(t1 - e->t0), s, e->stream));
+  AV_TRY(refresh_pref(e));
+  AV_HIP(hipStreamSynchronize(e->stream));
+  return AV_OK;
+}
+
+int av_is_accepted(av_engine* e, int64_t node, int64_t target, int32_t* out) {
+  AV_CHECK(e && out, AV_ERR_INVALID_ARG, "null argument");
+  *out = 0;
+  if (!local_node(e, node) || !local_target(e, target)) return AV_OK;  // no record -> false
+  uint32_t w = 0;
+  AV_TRY(av_read_records(e, node, node + 1, target, target + 1, &w));
+  if (((w >> 17) < (uint32_t)AV_FINALIZATION_SCORE)) *out = (int32_t)((w >> 16) & 1u);
+  return AV_OK;
+}
+
+int av_get_confidence(av_engine* e, int64_t node, int64_t target, uint16_t* out) {
+  AV_CHECK(e && out, AV_ERR_INVALID_ARG, "null argument");
+  if (!local_node(e, node) || !local_target(e, target)) return fail(AV_ERR_NOT_FOUND, "VoteRecord not found");
+  uint32_t w = 0;
+  AV_TRY(av_read_records(e, node, node + 1, target, target + 1, &w));
+  if ((w >> 17) >= (uint32_t)AV_FINALIZATION_SCORE) return fail(AV_ERR_NOT_FOUND, "VoteRecord not found");
+  *out = (uint16_t)(w >> 17);
+  return AV_OK;
+}
+
+int av_get_invs(av_engine* e, int64_t node, int64_t* out_targets, int64_t cap, int64_t* n_out) {
+  AV_CHECK(e && n_out && (cap == 0 || out_targets), AV_ERR_INVALID_ARG, "null argument");
+  *n_out = 0;
+  AV_CHECK(local_node(e, node), AV_ERR_INVALID_ARG, "node not in this shard");
+  std::vector<uint32_t> w((size_t)(e->t1 - e->t0));
+  AV_TRY(av_read_records(e, node, node + 1, e->t0, e->t1, w.data()));
+  int64_t cnt = 0;
+  for (int64_t tl = 0; tl < (int64_t)w.size() && cnt < AV_MAX_ELEMENT_POLL; ++tl) {
+    const bool live = (w[tl] >> 17) < (uint32_t)AV_FINALIZATION_SCORE;
+    const bool valid = (e->valid_host[tl >> 5] >> (tl & 31)) & 1u;
+    if (!live || !valid) continue;
+    if (cnt < cap) out_targets[cnt] = e->t0 + tl;
+    cnt++;
+  }
+  *n_out = cnt;
+  AV_CHECK(cnt <= cap, AV_ERR_OVERFLOW, "cap too small (%lld needed)", (long long)cnt);
+  return AV_OK;
+}
+
+// GetInvsForNextPoll for a node range (processor.go:144-170): counts, their device scan and the CSR
+// fill enqueued back to back, the fill writing offsets and targets straight into host-mapped pinned
+// staging (coalesced stores): one synchronization per call, then a host copy into the caller's arrays.
+int av_get_invs_batch(av_engine* e, int64_t n0, int64_t n1, int64_t* offsets, int32_t* targets, int64_t cap,
+                      int64_t* total) {
+  AV_ENTER(e);
+  AV_PEER_SYNC_CHECK(e);
+  AV_CHECK(offsets && total && (cap == 0 || targets), AV_ERR_INVALID_ARG, "null argument");
+  AV_CHECK(n0 >= e->n0 && n0 <= n1 && n1 <= e->n1, AV_ERR_INVALID_ARG, "node range outside this engine's shard");
+  const uint32_t n = (uint32_t)(n1 - n0);
+  *total = 0;
+  offsets[0] = 0;
+  if (!n) return AV_OK;
+  // staging: offsets (n + 1 int64) then up to min(cap, the largest possible poll sets) int32 targets
+  const uint64_t most = (uint64_t)n * (uint64_t)std::min<int64_t>(AV_MAX_ELEMENT_POLL, e->t1 - e->t0);
+  const uint64_t keep = std::min<uint64_t>((uint64_t)std::max<int64_t>(cap, 0), most);
+  const size_t hb = ((size_t)n + 1) * 8 + (size_t)keep * 4;
+  AV_HIP(e->invs_host.reserve(hb, avmem::Slack::kExact, hipHostMallocMapped));
+  void* dev_view = nullptr;
+  AV_HIP(hipHostGetDevicePointer(&dev_view, e->invs_host, 0));
+  auto* hoffs = static_cast<int64_t*>(e->invs_host.get());
+  auto* doffs = static_cast<int64_t*>(dev_view);
+  void* scratch = nullptr;
+  AV_TRY(engine_scratch(e, (size_t)avk::poll_sets_scratch_words(n) * 8, &scratch));
+  AV_HIP(avk::launch_poll_sets_batch(e->planes, e->valid, e->BL, (uint32_t)(n0 - e->n0), n, (uint32_t)e->t0, keep,
+                                     static_cast<uint64_t*>(scratch), doffs, reinterpret_cast<int32_t*>(doffs + n + 1),
+                                     e->stream));
+  AV_HIP(hipStreamSynchronize(e->stream));
+  *total = hoffs[n];
+  std::memcpy(offsets, hoffs, ((size_t)n + 1) * 8);
+  AV_CHECK(*total <= cap, AV_ERR_OVERFLOW, "cap too small (%lld needed)", (long long)*total);
+  if (*total) std::memcpy(targets, reinterpret_cast<const int32_t*>(hoffs + n + 1), (size_t)*total * 4);
+  return AV_OK;
+}
+
+int av_set_polling(av_engine* e, int64_t node, int32_t polls) {
+  if (e) e->facts.snapshot_written();
+  AV_ENTER(e);
+  AV_CHECK(local_node(e, node), AV_ERR_INVALID_ARG, "node %lld not in this shard", (long long)node);
+  AV_CHECK(e->peer_world <= 1, AV_ERR_UNSUPPORTED, "av_set_polling on a peer-push engine");
+  if (e->nopoll_host.empty()) {
+    e->nopoll_host.assign((e->NL + 31) / 32, 0u);
+    AV_HIP(e->nopoll.alloc(e->nopoll_host.size()));
+  }
+  const uint32_t nl = (uint32_t)(node - e->n0);
+  uint32_t& w = e->nopoll_host[nl >> 5];
+  w = polls ? (w & ~(1u << (nl & 31))) : (w | (1u << (nl & 31)));
+  AV_TRY(materialize_votes(e));  // rounds of non-polling networks run the first-generation kernel
+  AV_HIP(hipMemcpyAsync(e->nopoll, e->nopoll_host.data(), e->nopoll_host.size() * 4, hipMemcpyHostToDevice,
+                        e->stream));
+  AV_HIP(hipStreamSynchronize(e->stream));
+  e->any_nopoll = false;
+  for (uint32_t v : e->nopoll_host) e->any_nopoll |= v != 0;
+  return AV_OK;
+}
+
+int av_applied_votes(av_engine* e, int64_t* out) {
+  AV_TRY(counter_query(e, out));
+  return sum_shards(e, e->applied, out);
+}
+
+int av_finalized_count(av_engine* e, int64_t* out) {
+  AV_TRY(counter_query(e, out));
+  return sum_shards(e, e->finalized, out);
+}
+
+int av_live_records(av_engine* e, int32_t honest_only, int64_t* out) {
+  AV_TRY(counter_query(e, out));
+  AV_HIP(hipMemsetAsync(e->scratch_count, 0, 8, e->stream));
+  AV_HIP(avk::launch_count_live(e->planes, e->valid, e->byz, (uint32_t)e->n0, e->BL, e->L, honest_only,
+                                e->scratch_count, e->stream));
+  unsigned long long v = 0;
+  AV_HIP(hipMemcpyAsync(&v, e->scratch_count, 8, hipMemcpyDeviceToHost, e->stream));
+  AV_HIP(hipStreamSynchronize(e->stream));
+  *out = (int64_t)v;
+  return AV_OK;
+}
+
+// IsAccepted / GetConfidence over every Processor (processor.go:125-140) and the example's stop test
+// (main.go:143-162: a node is done when it holds no live record), tallied on the device: one pass
+// over the A and K planes (census.hip), read through the deferred count forms like av_read_records
+// and, like it, leaving them in place.
+int av_census(av_engine* e, int64_t n0, int64_t n1, int32_t honest_only, const av_census_out* out) {
+  AV_ENTER(e);
+  AV_PEER_SYNC_CHECK(e);
+  AV_CHECK(out && (out->target_classes || out->target_count_sum || out->node_classes || out->count_hist),
+           AV_ERR_INVALID_ARG, "no census output requested");
+  AV_CHECK(n0 >= e->n0 && n0 <= n1 && n1 <= e->n1, AV_ERR_INVALID_ARG, "range outside this engine's shard");
+  const size_t tn = (size_t)(e->t1 - e->t0), nn = (size_t)(n1 - n0);
+  if (out->target_classes) std::fill(out->target_classes, out->target_classes + tn * AV_CENSUS_CLASSES, (int64_t)0);
+  if (out->target_count_sum) std::fill(out->target_count_sum, out->target_count_sum + tn, (int64_t)0);
+  if (out->node_classes) std::fill(out->node_classes, out->node_classes + nn * AV_CENSUS_CLASSES, (int32_t)0);
+  if (out->count_hist) std::fill(out->count_hist, out->count_hist + 256, (int64_t)0);
+  if (!nn || !tn) return AV_OK;
+  // device sums: [tn][3] classes (live rejected, live accepted, absent accepted), [tn] count sums,
+  // [256] histogram, the nodes counted, one pad word; then the node rows (16-byte aligned)
+  const size_t head = tn * 4 + 256 + 2, head_bytes = head * 8;
+  void* buf = nullptr;
+  AV_TRY(engine_scratch(e, head_bytes + (out->node_classes ? nn * 16 : 0), &buf));
+  AV_HIP(hipMemsetAsync(buf, 0, head_bytes + (out->node_classes ? nn * 16 : 0), e->stream));
+  auto* d = static_cast<unsigned long long*>(buf);
+  avk::CensusParams p{};
+  p.planes = e->planes;
+  p.kpend = e->facts.k_pend ? e->kpend : nullptr;
+  p.valid = e->valid;
+  p.byz = e->byz;
+  p.tcls = out->target_classes ? d : nullptr;
+  p.tsum = out->target_count_sum ? d + tn * 3 : nullptr;
+  p.hist = out->count_hist ? d + tn * 4 : nullptr;
+  p.counted = d + tn * 4 + 256;
+  p.ncls = out->node_classes ? reinterpret_cast<int32_t*>(d + head) : nullptr;
+  p.BL = e->BL;
+  p.tn = (uint32_t)tn;
+  p.n0 = (uint32_t)e->n0;
+  p.honest_only = honest_only ? 1u : 0u;
+  AV_HIP(avk::launch_census(p, (uint32_t)(n0 - e->n0), (uint32_t)(n1 - e->n0), e->census_blocks, e->stream));
+  std::vector<unsigned long long> h(head);
+  AV_HIP(hipMemcpyAsync(h.data(), d, head_bytes, hipMemcpyDeviceToHost, e->stream));
+  if (out->node_classes)
+    AV_HIP(hipMemcpyAsync(out->node_classes, d + head, nn * 16, hipMemcpyDeviceToHost, e->stream));
+  AV_HIP(hipStreamSynchronize(e->stream));
+  AV_PEER_CHECK(e);
+  if (out->target_classes) {
+    const int64_t counted = (int64_t)h[tn * 4 + 256];
+    for (size_t t = 0; t < tn; ++t) {
+      int64_t* row = out->target_classes + t * AV_CENSUS_CLASSES;
+      row[AV_CENSUS_LIVE_REJECTED] = (int64_t)h[t * 3];
+      row[AV_CENSUS_LIVE_ACCEPTED] = (int64_t)h[t * 3 + 1];
+      row[AV_CENSUS_ABSENT_ACCEPTED] = (int64_t)h[t * 3 + 2];
+      // every counted node has exactly one class for the target
+      row[AV_CENSUS_ABSENT_REJECTED] = counted - row[0] - row[1] - row[3];
+    }
+  }
+  if (out->target_count_sum)
+    for (size_t t = 0; t < tn; ++t) out->target_count_sum[t] = (int64_t)h[tn * 3 + t];
+  if (out->count_hist)
+    for (size_t i = 0; i < 256; ++i) out->count_hist[i] = (int64_t)h[tn * 4 + i];
+  return AV_OK;
+}
+
+int av_alg_bytes(av_engine* e, int64_t* out) {
+  AV_TRY(counter_query(e, out));
+  return sum_shards(e, e->bytes, out);
+}
+
+int av_alg_bytes_reread(av_engine* e, int64_t* out) {
+  AV_TRY(counter_query(e, out));
+  return sum_shards(e, e->bytes + avk::kLogShards, out);
+}
+
+int av_changed_words(av_engine* e, int64_t* words, int64_t* segments) {
+  AV_TRY(counter_query(e, words));
+  AV_TRY(sum_shards(e, e->changed, words));
+  return segments ? sum_shards(e, e->changed + avk::kLogShards, segments) : AV_OK;
+}
+
+int av_net_quiet_rounds(av_engine* e, int64_t* out) {
+  AV_TRY(counter_query(e, out));
+  uint32_t v = 0;
+  AV_HIP(hipMemcpyAsync(&v, e->nq + 2, 4, hipMemcpyDeviceToHost, e->stream));
+  AV_HIP(hipStreamSynchronize(e->stream));
+  *out = (int64_t)v;
+  return AV_OK;
+}
+
+int av_read_pref(av_engine* e, int64_t n0, int64_t n1, int64_t t0, int64_t t1, uint8_t* out) {
+  AV_ENTER(e);
+  AV_PEER_SYNC_CHECK(e);
+  AV_CHECK(out && n0 >= 0 && n0 <= n1 && n1 <= e->N && t0 >= e->t0 && t0 <= t1 && t1 <= e->t1,
+           AV_ERR_INVALID_ARG, "bad range");
+  const size_t rows = (size_t)(n1 - n0);
+  std::vector<uint32_t> w(rows * e->BL);
+  if (rows) AV_TRY(av_read_pref_words(e, n0, n1, w.data()));
+  const int64_t W = t1 - t0;
+  for (size_t r = 0; r < rows; ++r)
+    for (int64_t t = t0; t < t1; ++t) {
+      const int64_t tl = t - e->t0;
+      out[r * W + (t - t0)] = (uint8_t)((w[r * e->BL + (tl >> 5)] >> (tl & 31)) & 1u);
+    }
+  return AV_OK;
+}
+
+int av_read_pref_words(av_engine* e, int64_t n0, int64_t n1, uint32_t* out) {
+  AV_ENTER(e);
+  AV_PEER_SYNC_CHECK(e);
+  AV_CHECK(out && n0 >= 0 && n0 <= n1 && n1 <= e->N, AV_ERR_INVALID_ARG, "bad range");
+  const size_t words = (size_t)(n1 - n0) * e->BL;
+  if (!words) return AV_OK;
+  AV_HIP(hipMemcpy2DAsync(out, (size_t)e->BL * 4, e->pref[e->cur] + (size_t)n0 * e->PS, (size_t)e->PS * 4,
+                          (size_t)e->BL * 4, (size_t)(n1 - n0), hipMemcpyDeviceToHost, e->stream));
+  AV_HIP(hipStreamSynchronize(e->stream));
+  return AV_OK;
+}
+
+int av_sample_peers(av_engine* e, int64_t round, int64_t n0, int64_t n1, int32_t* out) {
+  AV_ENTER(e);
+  AV_CHECK(out && n0 >= 0 && n0 <= n1 && n1 <= e->N && round >= 0, AV_ERR_INVALID_ARG, "bad range");
+  const size_t n = (size_t)(n1 - n0) * e->k;
+  if (!n) return AV_OK;
+  avmem::DevBuf<uint32_t> s;
+  AV_HIP(s.alloc(n));
+  AV_HIP(avk::launch_sample_peers(e->cfg.seed, (uint32_t)e->N, (uint32_t)n0, (uint32_t)n1, (uint32_t)round, e->k,
+                                  e->cfg.peer_mode, s, e->stream));
+  AV_HIP(hipMemcpyAsync(out, s, n * 4, hipMemcpyDeviceToHost, e->stream));
+  AV_HIP(hipStreamSynchronize(e->stream));
+  return AV_OK;
+}
+
+int av_pushed_words(av_engine* e, int64_t* out) {
+  AV_TRY(counter_query(e, out));
+  return sum_shards(e, e->changed + 2 * avk::kLogShards, out);
+}
+
+}  // extern "C"

@@ -3,6 +3,7 @@ symbol include/avhip.h declares (no compute calls: there is no GPU here)."""
 import ctypes
 import os
 import re
+import subprocess
 
 import avhip
 
@@ -23,6 +24,18 @@ def test_library_exports_every_header_symbol():
     lib = ctypes.CDLL(avhip.LIB_PATH)
     missing = [s for s in header_symbols() if not hasattr(lib, s)]
     assert not missing, missing
+
+
+def test_library_exports_only_header_symbols():
+    """The defined, unmangled text symbols of the dynamic table are exactly what
+    include/avhip.h declares: the engine's host objects are built with hidden
+    visibility, so a helper left in an extern "C" block no longer leaks under a
+    generic C name (the .hip objects export no such symbol either)."""
+    out = subprocess.run(["nm", "-D", "--defined-only", avhip.LIB_PATH], check=True, capture_output=True,
+                         text=True).stdout
+    rows = [line.split() for line in out.splitlines()]
+    exported = sorted(r[2] for r in rows if len(r) == 3 and r[1] == "T" and not r[2].startswith("_Z"))
+    assert exported == header_symbols()
 
 
 def test_abi_version_and_strings():
