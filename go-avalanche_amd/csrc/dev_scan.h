@@ -1,6 +1,6 @@
 // Hand-written device-wide primitives for CDNA4 (64-lane waves, LDS), used by
 // StatusUpdate delivery (log_ops.hip), the batched drop-in RegisterVotes
-// grouping and the batched GetInvsForNextPoll (kernels.hip):
+// grouping (dropin.hip) and the batched GetInvsForNextPoll (kernels.hip):
 //  * launch_scan: exclusive prefix sum of n values into u64 out[0..n], out[n] =
 //    the total. Reduce-then-scan over tiles of 4096 values (256 threads x 16
 //    chunks, striped so every load is coalesced); the tile partials are scanned

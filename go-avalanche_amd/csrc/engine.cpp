@@ -1,4 +1,4 @@
-// libavhip.so — C ABI (include/avhip.h) over the CDNA4 kernels in kernels.hip.
+// libavhip.so — C ABI (include/avhip.h) over the CDNA4 kernels (csrc/*.hip, kernels.h).
 //
 // The engine owns all device memory: the bit-sliced VoteRecord planes, the two
 // published-preference snapshots, validity / Byzantine bitsets, the sharded

@@ -1,9 +1,14 @@
-// Internal interface between the C-ABI engine (engine.cpp) and the CDNA4
-// kernels (kernels.hip). Not part of the public ABI (include/avhip.h).
+// Internal interface between the host side of the C ABI (engine*.cpp) and the
+// CDNA4 kernels (*.hip). Not part of the public ABI (include/avhip.h). First
+// the state layout with its constants and host/device helpers, then
+// RoundParams, then one section per .hip file in the Makefile's order: that
+// file's parameter structs and the launchers it defines.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 namespace avk {
 
@@ -20,7 +25,7 @@ namespace avk {
 //           never added). A dead record keeps A = published decision.
 // A *lane* is one (local node, local block) pair, g = node_local * BL + b.
 // Lanes are grouped in tiles of 64 (one wavefront); a tile stores its 25
-// planes in one contiguous 6400-byte span (plane_off() in kernels.hip):
+// planes in one contiguous 6400-byte span (plane_off() in round_common.h):
 // V0-3, V4-7, K0-3, K4-7 as lane-interleaved 16-byte groups (one dwordx4 per
 // lane = 1 KiB contiguous per wave-instruction), then C0..C7 and A as dword
 // planes (256 B per wave-instruction).
@@ -55,11 +60,68 @@ __host__ __device__ constexpr uint32_t pref_stride(uint32_t BL) {
   return BL > 32u ? (BL + 31u) / 32u * 32u : (BL <= 1u ? 1u : 1u << (32 - __builtin_clz(BL - 1u)));
 }
 
-// Device pointers of every rank's copy of a buffer, passed by value (kernel arguments: static
-// indices keep them in SGPRs, no table load per use).
-struct PeerPtrs {
-  uint32_t* p[kMaxPeers + 1];
-};
+// Tile words of the deferred forms (RoundParams::kpend, ::vstale below).
+constexpr uint32_t kPendAllLive = 0x80000000u;
+// kpend bit 30 (kHiVirt, k = 8 sweep rounds while every count is < 16; option "k_hi_virtual"): the
+// tile's K4..K7 group is not stored: K4 = K5 = K6 = 0 on every record and K7 = the records past the
+// engine's last target (k_init_planes: every existing target's record live, none deleted since).
+// Set by the fresh round; kept by a warm round whose counts all stay < 16 with no deletion (or
+// that defers the tile's count planes); written back by the round that breaks it, kconsume and
+// k_materialize (k_read_records_v reads it virtually).
+constexpr uint32_t kHiVirt = 0x40000000u;
+__host__ __device__ inline uint32_t real_mask(uint32_t tn, uint32_t b) {  // existing targets of local block b
+  const uint32_t rem = tn > b * 32u ? tn - b * 32u : 0u;
+  return rem >= 32u ? ~0u : ((1u << rem) - 1u);
+}
+constexpr uint32_t kVStale = 1u, kVUniform = 2u, kVMask = 3u, kCAll = 4u;
+
+// Division by the (runtime) block count BL without a hardware divide:
+// Granlund-Montgomery round-up magic, exact for every 32-bit n.
+inline void bl_divider(uint32_t d, uint32_t& magic, uint32_t& sh1, uint32_t& sh2) {
+  uint32_t l = 0;
+  while ((1ull << l) < d) ++l;
+  magic = (uint32_t)((((1ull << l) - d) << 32) / d + 1);
+  sh1 = l < 1 ? l : 1;
+  sh2 = l > 1 ? l - 1 : 0;
+}
+
+// A lane (32-record block) with many StatusUpdates in one round logs one dense
+// record instead of single entries: u32 words [key lo, key hi (pack_update
+// with the block's first target, slot 0, status 0), E_0 .. E_{k-1} (updated
+// records per slot), A (final accepted plane), died (records deleted this
+// round)], padded to whole u64 words; fetch expands it. Dense when its size
+// is at most that of the singles: 8 * count >= 8 * dense_words(k).
+__host__ __device__ constexpr uint32_t dense_words(uint32_t k) { return (k + 5u) / 2u; }  // u64 words
+__host__ __device__ constexpr uint32_t dense_min(uint32_t k) { return dense_words(k); }   // updates
+
+// Medium lane records (k = 8 round kernels, round_common.h emit_store_med): a slot record of four
+// u64 = u32 words [key lo, key hi (pack_update with the block's first target, slot 0, status 0), S
+// (bits 0-7: slots with updates; bit 8 kMedS4Died: the last word is the died plane), A (final
+// accepted plane), E of the first, second, third and fourth slot with updates (zero past the last;
+// the fourth is the died plane when flagged)]. Logged by a lane with >= 2 updates in at most 4 slots
+// (at most 3 when a record of it was deleted this round); other lanes with >= 2 updates log a dense
+// record. Expanded as a dense record over the slots S names.
+constexpr uint32_t kMedS4Died = 1u << 8;
+__host__ __device__ constexpr uint32_t med_rec_words() { return 4u; }  // u64 per medium record
+
+// Update-log entry (one StatusUpdate, avalanche.go:59-62):
+//   [63:S] round - log_base | [S-1:28] node | [27:24] slot | [23:2] target | [1:0] status
+// S = the engine's round shift: 28 + max(24, bits of N) (52 below 2^24 nodes, include/avhip.h).
+// Ascending order of the packed word == canonical (round, node, slot, target).
+__host__ __device__ inline uint64_t pack_update(uint32_t round_rel, uint32_t node, uint32_t slot,
+                                                uint32_t target, uint32_t status, uint32_t round_shift) {
+  return ((uint64_t)round_rel << round_shift) | ((uint64_t)node << 28) | ((uint64_t)slot << 24) |
+         ((uint64_t)target << 2) | (uint64_t)status;
+}
+
+// A drop-in vote as the host packs it: the target's local index, "unknown hash" (outside this
+// engine's targets: skipped, processor.go:95-99), err == 0 (yes) and int32(err) >= 0 (considered),
+// vote.go:55-56.
+constexpr uint32_t kDropUnknown = 1u << 29, kDropYes = 1u << 30, kDropCons = 1u << 31, kDropTl = (1u << 22) - 1u;
+__host__ __device__ inline uint32_t dropin_word(int64_t tl, bool local, uint32_t err) {
+  return (local ? (uint32_t)tl & kDropTl : kDropUnknown) | (err == 0u ? kDropYes : 0u) |
+         ((int32_t)err >= 0 ? kDropCons : 0u);
+}
 
 struct RoundParams {
   uint32_t* planes;
@@ -263,114 +325,21 @@ struct RoundParams {
   uint32_t wave_dense; // k = 8 sweep (A/B option "wave_dense"): a wave with >= wave_dense lanes holding updates
                        // logs every such lane as a dense record (one store branch, no slot-word network); 0 off
 };
-constexpr uint32_t kPendAllLive = 0x80000000u;
-// kpend bit 30 (kHiVirt, k = 8 sweep rounds while every count is < 16; option "k_hi_virtual"): the
-// tile's K4..K7 group is not stored: K4 = K5 = K6 = 0 on every record and K7 = the records past the
-// engine's last target (k_init_planes: every existing target's record live, none deleted since).
-// Set by the fresh round; kept by a warm round whose counts all stay < 16 with no deletion (or
-// that defers the tile's count planes); written back by the round that breaks it, kconsume and
-// k_materialize (k_read_records_v reads it virtually).
-constexpr uint32_t kHiVirt = 0x40000000u;
-__host__ __device__ inline uint32_t real_mask(uint32_t tn, uint32_t b) {  // existing targets of local block b
-  const uint32_t rem = tn > b * 32u ? tn - b * 32u : 0u;
-  return rem >= 32u ? ~0u : ((1u << rem) - 1u);
-}
-constexpr uint32_t kVStale = 1u, kVUniform = 2u, kVMask = 3u, kCAll = 4u;
 
-// Division by the (runtime) block count BL without a hardware divide:
-// Granlund-Montgomery round-up magic, exact for every 32-bit n.
-inline void bl_divider(uint32_t d, uint32_t& magic, uint32_t& sh1, uint32_t& sh2) {
-  uint32_t l = 0;
-  while ((1ull << l) < d) ++l;
-  magic = (uint32_t)((((1ull << l) - d) << 32) / d + 1);
-  sh1 = l < 1 ? l : 1;
-  sh2 = l > 1 ? l - 1 : 0;
+// Dispatch on the runtime k: f(std::integral_constant<int, K>{}) for k = K in [1, MAXK], so that a
+// launcher instantiates its kernels for exactly that range; hipErrorInvalidValue outside it.
+// Ascending, as the switches it replaces were: instantiated from MAXK down, the k = 1 kernels of
+// round_firstgen.hip come out with a few instructions in another order.
+template <int MAXK, int K = 1, typename F>
+hipError_t dispatch_k(int k, F&& f) {
+  if constexpr (K <= MAXK) {
+    return k == K ? f(std::integral_constant<int, K>{}) : dispatch_k<MAXK, K + 1>(k, f);
+  } else {
+    return hipErrorInvalidValue;
+  }
 }
 
-// A lane (32-record block) with many StatusUpdates in one round logs one dense
-// record instead of single entries: u32 words [key lo, key hi (pack_update
-// with the block's first target, slot 0, status 0), E_0 .. E_{k-1} (updated
-// records per slot), A (final accepted plane), died (records deleted this
-// round)], padded to whole u64 words; fetch expands it. Dense when its size
-// is at most that of the singles: 8 * count >= 8 * dense_words(k).
-__host__ __device__ constexpr uint32_t dense_words(uint32_t k) { return (k + 5u) / 2u; }  // u64 words
-__host__ __device__ constexpr uint32_t dense_min(uint32_t k) { return dense_words(k); }   // updates
-
-// Medium lane records (k = 8 round kernels, round_common.h emit_store_med): a slot record of four
-// u64 = u32 words [key lo, key hi (pack_update with the block's first target, slot 0, status 0), S
-// (bits 0-7: slots with updates; bit 8 kMedS4Died: the last word is the died plane), A (final
-// accepted plane), E of the first, second, third and fourth slot with updates (zero past the last;
-// the fourth is the died plane when flagged)]. Logged by a lane with >= 2 updates in at most 4 slots
-// (at most 3 when a record of it was deleted this round); other lanes with >= 2 updates log a dense
-// record. Expanded as a dense record over the slots S names.
-constexpr uint32_t kMedS4Died = 1u << 8;
-__host__ __device__ constexpr uint32_t med_rec_words() { return 4u; }  // u64 per medium record
-
-// Update-log entry (one StatusUpdate, avalanche.go:59-62):
-//   [63:S] round - log_base | [S-1:28] node | [27:24] slot | [23:2] target | [1:0] status
-// S = the engine's round shift: 28 + max(24, bits of N) (52 below 2^24 nodes, include/avhip.h).
-// Ascending order of the packed word == canonical (round, node, slot, target).
-__host__ __device__ inline uint64_t pack_update(uint32_t round_rel, uint32_t node, uint32_t slot,
-                                                uint32_t target, uint32_t status, uint32_t round_shift) {
-  return ((uint64_t)round_rel << round_shift) | ((uint64_t)node << 28) | ((uint64_t)slot << 24) |
-         ((uint64_t)target << 2) | (uint64_t)status;
-}
-
-hipError_t launch_round(const RoundParams& p, int k, bool replay, bool capped, hipStream_t s);
-// k_replay_node: p.fuse_rounds replay rounds of every node in one launch (capped engines, k <= 8);
-// nodes that reach count 120 are left to the exact pass from that round on (node_flags)
-hipError_t launch_replay_node(const RoundParams& p, int k, hipStream_t s);
-// Persistent streaming round kernel (round_sweep.hip), uncapped path, k <= 8:
-// `blocks` workgroups of 256 threads sweep the tiles; 0 = one wave per tile.
-// mode: the round plan's (round_plan.h plan_round)
-// ref_written (may be null): whether the launch wrote p.rflag_out (only the walking warm mode does)
-enum class SweepMode : int;
-hipError_t launch_round_sweep(const RoundParams& p, int k, SweepMode mode, uint32_t blocks, hipStream_t s,
-                              bool* ref_written = nullptr);
-// Capped round (M > 4096, k <= 8; round_node.hip): one workgroup per node;
-// nodes that may finalize a record this round are flagged in p.node_flags and
-// left to the exact pass (k_round_capped over the flagged nodes only), which
-// the caller may skip when no count can have reached 120 (exact_pass false).
-hipError_t launch_round_node(const RoundParams& p, int k, bool replay, bool exact_pass, hipStream_t s);
-// Resident 256-thread workgroups per CU for the sweep kernel and the CU count.
-hipError_t round_sweep_occupancy(int k, bool replay, int* blocks_per_cu, int* cus);
-// k_materialize: both write-backs in one pass over runs of p.mat_run tiles per wave; tiles with
-// nothing deferred are skipped with no memory access. k = 8 only.
-// do_v: the V planes of stale tiles (p.vstale, p.pref_prev, p.round = the round after the one that
-// left them stale); do_k: the pending +8 steps of deferred count planes (p.kpend), then cleared.
-hipError_t launch_materialize(const RoundParams& p, bool do_v, bool do_k, hipStream_t s);
-
-// Need-masked exchange (DESIGN.md §5): the rows each rank's nodes draw in the rounds of one window.
-// need_draw: mine[w][N] = 1 for every row drawn by a local node in round round0 + w (w < W).
-// need_push: the bits of mine for peer d's rows into peer d's needin[par][rank][w][NLw] (words).
-// need_combine: needmask[w][nl] = the peers (push order) whose nodes draw local row nl in round
-// round0 + w (ref_local: the reference row, read by every rank, is needed by all).
-constexpr uint32_t kNeedWin = 16;  // rounds per need window
-constexpr uint32_t kPushQ = 16;    // tiles per wave whose pushes the sweep queues in LDS
-hipError_t launch_need_draw(uint64_t seed, uint32_t n_nodes, uint32_t n0, uint32_t NL, uint32_t round0, uint32_t W,
-                            int k, int mode, uint8_t* mine, hipStream_t s);
-hipError_t launch_need_push(const uint8_t* mine, uint32_t n_nodes, uint32_t NL, uint32_t W, uint32_t world,
-                            uint32_t rank, uint32_t par, PeerPtrs needin, hipStream_t s);
-hipError_t launch_need_combine(const uint32_t* needin, uint32_t world, uint32_t rank, uint32_t par, uint32_t W,
-                               uint32_t NL, uint32_t ref_local, uint8_t* needmask, hipStream_t s);
-
-// Peer-push exchange helpers (kernels.hip). push_rows: copy words [w0, w1) of
-// a local snapshot buffer into the same range of every peer replica.
-hipError_t launch_push_rows(const uint32_t* src, PeerPtrs dst, uint32_t n_dst, uint64_t w0, uint64_t w1,
-                            hipStream_t s);
-// Barrier across the ranks of a node-sharded network: lane i writes `seq`
-// into slot `rank` of rank i's arrival array (arrive[i], system scope), then
-// waits until every slot of its own array (arrive[rank]) has reached `seq`.
-// Gives up after timeout_ticks of the wall clock and sets *err (later barriers then return at once).
-hipError_t launch_peer_barrier(PeerPtrs arrive, uint32_t world, uint32_t rank, uint32_t seq, uint32_t* err,
-                               uint64_t timeout_ticks, hipStream_t s, const uint32_t* slot = nullptr,
-                               PeerPtrs slot_dst = PeerPtrs{}, uint32_t wait = 1u);
-// (slot: this rank's uniform-rows mismatch slot of the snapshot the round wrote, copied into every
-// peer's replica (slot_dst.p[i]: rank i's copy) before the arrival; wait = 0: no arrival and no wait
-// (the serial peer group, whose stream order is the barrier))
-// Wall-clock ticks of a timeout (the device's wall clock rate; queried once per engine).
-hipError_t peer_timeout_ticks(int device, uint32_t timeout_ms, uint64_t* ticks);
-
+// ---- kernels.hip: engine state
 struct InitParams {
   uint32_t* planes;
   uint32_t* pref;       // [N_pad][PS]
@@ -383,7 +352,65 @@ struct InitParams {
 };
 hipError_t launch_init(const InitParams& p, hipStream_t s);
 hipError_t launch_byz(uint32_t* byz, uint32_t n_nodes, uint64_t seed, uint32_t threshold, hipStream_t s);
+hipError_t launch_read_records(const uint32_t* planes, uint32_t BL, uint32_t nl0, uint32_t nl1,
+                               uint32_t tl0, uint32_t tl1, uint32_t* out, hipStream_t s);
+// Canonical words without writing back deferred state (k_read_records_v):
+// p = the engine's round parameters with p.vv = "some tile may be stale" and
+// p.klazy = "some tile may hold pending count steps".
+hipError_t launch_read_records_virtual(const RoundParams& p, uint32_t nl0, uint32_t nl1, uint32_t tl0, uint32_t tl1,
+                                       uint32_t* out, hipStream_t s);
+hipError_t launch_write_records(uint32_t* planes, uint32_t BL, uint32_t nl0, uint32_t nl1, uint32_t tl0,
+                                uint32_t tl1, const uint32_t* in, hipStream_t s);
+hipError_t launch_refresh_pref(uint32_t pub_mode, const uint32_t* planes, uint32_t* pref, const uint32_t* byz,
+                               uint32_t n0, uint32_t NL, uint32_t BL, uint32_t PS, uint32_t round, hipStream_t s);
+hipError_t launch_sample_peers(uint64_t seed, uint32_t n_nodes, uint32_t a, uint32_t b, uint32_t round,
+                               int k, int mode, uint32_t* out, hipStream_t s);
+hipError_t launch_gen_replay(uint64_t seed, uint32_t n0, uint32_t NL, uint32_t BL, uint32_t L, uint32_t Lpad,
+                             uint32_t t0, uint32_t n_targets, uint32_t round, int k, uint32_t* out,
+                             hipStream_t s);
+hipError_t launch_count_live(const uint32_t* planes, const uint32_t* valid, const uint32_t* byz, uint32_t n0,
+                             uint32_t BL, uint32_t L, int honest_only, unsigned long long* out, hipStream_t s);
+// Batched poll sets (GetInvsForNextPoll of nodes [nl0, nl0 + n)): the per-node counts, their device
+// scan into offsets (n + 1, u64) and the CSR targets in one stream-ordered sequence; entries at or past
+// cap are not written. offs_out / targets_out may be host-mapped pinned memory (hipHostGetDevicePointer):
+// the fill kernel's stores are coalesced. scratch: poll_sets_scratch_words(n) u64.
+uint64_t poll_sets_scratch_words(uint32_t n);
+hipError_t launch_poll_sets_batch(const uint32_t* planes, const uint32_t* valid, uint32_t BL, uint32_t nl0,
+                                  uint32_t n, uint32_t t0, uint64_t cap, uint64_t* scratch, int64_t* offs_out,
+                                  int32_t* targets_out, hipStream_t s);
 
+// ---- round_firstgen.hip: the first-generation round kernels, k <= 16
+hipError_t launch_round(const RoundParams& p, int k, bool replay, bool capped, hipStream_t s);
+// After a round with the example's responder (pub_mode 2): re-create the
+// records queried this round that their responder did not hold.
+hipError_t launch_readd(const RoundParams& p, hipStream_t s);
+
+// ---- round_sweep.hip: the persistent streaming round, uncapped, k <= 8
+// k_round_sweep: `blocks` workgroups of 256 threads sweep the tiles; 0 = one wave per tile.
+// mode: the round plan's (round_plan.h plan_round)
+// ref_written (may be null): whether the launch wrote p.rflag_out (only the walking warm mode does)
+enum class SweepMode : int;
+hipError_t launch_round_sweep(const RoundParams& p, int k, SweepMode mode, uint32_t blocks, hipStream_t s,
+                              bool* ref_written = nullptr);
+// Resident 256-thread workgroups per CU for the sweep kernel and the CU count.
+hipError_t round_sweep_occupancy(int k, bool replay, int* blocks_per_cu, int* cus);
+// k_materialize: both write-backs in one pass over runs of p.mat_run tiles per wave; tiles with
+// nothing deferred are skipped with no memory access. k = 8 only.
+// do_v: the V planes of stale tiles (p.vstale, p.pref_prev, p.round = the round after the one that
+// left them stale); do_k: the pending +8 steps of deferred count planes (p.kpend), then cleared.
+hipError_t launch_materialize(const RoundParams& p, bool do_v, bool do_k, hipStream_t s);
+
+// ---- round_node.hip: the capped round, k <= 8
+// k_replay_node: p.fuse_rounds replay rounds of every node in one launch (capped engines, k <= 8);
+// nodes that reach count 120 are left to the exact pass from that round on (node_flags)
+hipError_t launch_replay_node(const RoundParams& p, int k, hipStream_t s);
+// Capped round (M > 4096, k <= 8): one workgroup per node; nodes that may
+// finalize a record this round are flagged in p.node_flags and left to the
+// exact pass (round_firstgen.hip k_round_capped over the flagged nodes only), which
+// the caller may skip when no count can have reached 120 (exact_pass false).
+hipError_t launch_round_node(const RoundParams& p, int k, bool replay, bool exact_pass, hipStream_t s);
+
+// ---- dropin.hip: RegisterVotes and AddTargetToReconcile
 struct DropInParams {
   uint32_t* planes;
   uint32_t* pref;          // current published snapshot row for the node
@@ -407,14 +434,6 @@ struct DropInParams {
   const uint32_t* grp_off;
   uint32_t n_groups;
 };
-// A drop-in vote as the host packs it: the target's local index, "unknown hash" (outside this
-// engine's targets: skipped, processor.go:95-99), err == 0 (yes) and int32(err) >= 0 (considered),
-// vote.go:55-56.
-constexpr uint32_t kDropUnknown = 1u << 29, kDropYes = 1u << 30, kDropCons = 1u << 31, kDropTl = (1u << 22) - 1u;
-__host__ __device__ inline uint32_t dropin_word(int64_t tl, bool local, uint32_t err) {
-  return (local ? (uint32_t)tl & kDropTl : kDropUnknown) | (err == 0u ? kDropYes : 0u) |
-         ((int32_t)err >= 0 ? kDropCons : 0u);
-}
 hipError_t launch_register_votes(const DropInParams& p, hipStream_t s);
 // Fast path of a batch whose Responses each have strictly ascending targets: one workgroup per node
 // (its Responses in order), the first vote of each (node, block) run applies the run.
@@ -435,23 +454,61 @@ struct AddParams {
   uint32_t pub_mode;
 };
 hipError_t launch_add_targets(const AddParams& p, hipStream_t s);
+// Drop-in batch grouping: stable radix sort of (lane key, position) into (keys_s, perm_s) (keys_t,
+// perm_t: the other buffer set), run-length encoding into lanes / offs (n_runs + 1) / *n_runs, and the
+// (vote index, packed vote) entries in grouped order. scratch: group_votes_scratch_words(n) u64.
+uint64_t group_votes_scratch_words(uint32_t n);
+hipError_t launch_group_votes(uint64_t* scratch, const uint32_t* keys, const uint32_t* vidx, const uint32_t* info,
+                              uint32_t n, int key_bits, uint32_t* keys_s, uint32_t* perm_s, uint32_t* keys_t,
+                              uint32_t* perm_t, uint32_t* lanes, uint32_t* offs, uint32_t* n_runs, uint32_t* entries,
+                              hipStream_t s);
 
-hipError_t launch_read_records(const uint32_t* planes, uint32_t BL, uint32_t nl0, uint32_t nl1,
-                               uint32_t tl0, uint32_t tl1, uint32_t* out, hipStream_t s);
-// Canonical words without writing back deferred state (kernels.hip
-// k_read_records_v): p = the engine's round parameters with p.vv = "some tile
-// may be stale" and p.klazy = "some tile may hold pending count steps".
-hipError_t launch_read_records_virtual(const RoundParams& p, uint32_t nl0, uint32_t nl1, uint32_t tl0, uint32_t tl1,
-                                       uint32_t* out, hipStream_t s);
+// ---- peer_ops.hip: the exchange of node-sharded engines
+// Device pointers of every rank's copy of a buffer, passed by value (kernel arguments: static
+// indices keep them in SGPRs, no table load per use).
+struct PeerPtrs {
+  uint32_t* p[kMaxPeers + 1];
+};
 
-// Device-side StatusUpdate delivery (log_ops.hip).
+// Need-masked exchange (DESIGN.md §5): the rows each rank's nodes draw in the rounds of one window.
+// need_draw: mine[w][N] = 1 for every row drawn by a local node in round round0 + w (w < W).
+// need_push: the bits of mine for peer d's rows into peer d's needin[par][rank][w][NLw] (words).
+// need_combine: needmask[w][nl] = the peers (push order) whose nodes draw local row nl in round
+// round0 + w (ref_local: the reference row, read by every rank, is needed by all).
+constexpr uint32_t kNeedWin = 16;  // rounds per need window
+constexpr uint32_t kPushQ = 16;    // tiles per wave whose pushes the sweep queues in LDS
+hipError_t launch_need_draw(uint64_t seed, uint32_t n_nodes, uint32_t n0, uint32_t NL, uint32_t round0, uint32_t W,
+                            int k, int mode, uint8_t* mine, hipStream_t s);
+hipError_t launch_need_push(const uint8_t* mine, uint32_t n_nodes, uint32_t NL, uint32_t W, uint32_t world,
+                            uint32_t rank, uint32_t par, PeerPtrs needin, hipStream_t s);
+hipError_t launch_need_combine(const uint32_t* needin, uint32_t world, uint32_t rank, uint32_t par, uint32_t W,
+                               uint32_t NL, uint32_t ref_local, uint8_t* needmask, hipStream_t s);
+
+// push_rows: copy words [w0, w1) of a local snapshot buffer into the same
+// range of every peer replica.
+hipError_t launch_push_rows(const uint32_t* src, PeerPtrs dst, uint32_t n_dst, uint64_t w0, uint64_t w1,
+                            hipStream_t s);
+// Barrier across the ranks of a node-sharded network: lane i writes `seq`
+// into slot `rank` of rank i's arrival array (arrive[i], system scope), then
+// waits until every slot of its own array (arrive[rank]) has reached `seq`.
+// Gives up after timeout_ticks of the wall clock and sets *err (later barriers then return at once).
+hipError_t launch_peer_barrier(PeerPtrs arrive, uint32_t world, uint32_t rank, uint32_t seq, uint32_t* err,
+                               uint64_t timeout_ticks, hipStream_t s, const uint32_t* slot = nullptr,
+                               PeerPtrs slot_dst = PeerPtrs{}, uint32_t wait = 1u);
+// (slot: this rank's uniform-rows mismatch slot of the snapshot the round wrote, copied into every
+// peer's replica (slot_dst.p[i]: rank i's copy) before the arrival; wait = 0: no arrival and no wait
+// (the serial peer group, whose stream order is the barrier))
+// Wall-clock ticks of a timeout (the device's wall clock rate; queried once per engine).
+hipError_t peer_timeout_ticks(int device, uint32_t timeout_ms, uint64_t* ticks);
+
+// ---- log_ops.hip: StatusUpdate delivery
 // Digest {count, sum, xor} of splitmix64(packed word) over every pending update
 // of nodes [node0, node1).
 hipError_t launch_log_digest(const uint64_t* log, const uint32_t* counts, uint32_t cap, const uint64_t* dlog,
                              const uint32_t* dcounts, uint32_t dcap, const uint64_t* mlog, const uint32_t* mcounts,
                              uint32_t mcap, uint32_t shards, uint32_t k, uint32_t node0, uint32_t node1,
                              uint32_t round_shift, unsigned long long* out, hipStream_t s);
-// Canonical order of the pending StatusUpdates (log_ops.hip): a counting sort by (round, node) bucket
+// Canonical order of the pending StatusUpdates: a counting sort by (round, node) bucket
 // for rounds [r0, r0 + nr) of the log (round_rel < r_total), then one wave per bucket writing its
 // updates in (slot, target) order, as packed words (out + ubase + the bucket's update offset) or as
 // compact groups (cout + cbase + its byte offset; index entries into cidx). Reads the log counters on
@@ -475,32 +532,11 @@ hipError_t launch_encode_log(const EncodeParams& p, uint64_t entries, void* scra
 // Copy bytes (rounded up to 16; both buffers 16-B aligned and that large) from device memory into
 // host-mapped pinned memory with `blocks` workgroups (k_stream_out).
 hipError_t launch_stream_out(const void* src, void* dst, uint64_t bytes, uint32_t blocks, hipStream_t s);
-// diagnostics: read `bytes` of src once (log_ops.hip k_touch)
+// diagnostics: read `bytes` of src once (k_touch)
 hipError_t launch_touch(const void* src, uint64_t bytes, uint32_t* sink, hipStream_t s);
-// Drop-in batch grouping: stable radix sort of (lane key, position) into (keys_s, perm_s) (keys_t,
-// perm_t: the other buffer set), run-length encoding into lanes / offs (n_runs + 1) / *n_runs, and the
-// (vote index, packed vote) entries in grouped order. scratch: group_votes_scratch_words(n) u64.
-uint64_t group_votes_scratch_words(uint32_t n);
-hipError_t launch_group_votes(uint64_t* scratch, const uint32_t* keys, const uint32_t* vidx, const uint32_t* info,
-                              uint32_t n, int key_bits, uint32_t* keys_s, uint32_t* perm_s, uint32_t* keys_t,
-                              uint32_t* perm_t, uint32_t* lanes, uint32_t* offs, uint32_t* n_runs, uint32_t* entries,
-                              hipStream_t s);
 
-hipError_t launch_write_records(uint32_t* planes, uint32_t BL, uint32_t nl0, uint32_t nl1, uint32_t tl0,
-                                uint32_t tl1, const uint32_t* in, hipStream_t s);
-// After a round with the example's responder (pub_mode 2): re-create the
-// records queried this round that their responder did not hold.
-hipError_t launch_readd(const RoundParams& p, hipStream_t s);
-hipError_t launch_refresh_pref(uint32_t pub_mode, const uint32_t* planes, uint32_t* pref, const uint32_t* byz,
-                               uint32_t n0, uint32_t NL, uint32_t BL, uint32_t PS, uint32_t round, hipStream_t s);
-hipError_t launch_sample_peers(uint64_t seed, uint32_t n_nodes, uint32_t a, uint32_t b, uint32_t round,
-                               int k, int mode, uint32_t* out, hipStream_t s);
-hipError_t launch_gen_replay(uint64_t seed, uint32_t n0, uint32_t NL, uint32_t BL, uint32_t L, uint32_t Lpad,
-                             uint32_t t0, uint32_t n_targets, uint32_t round, int k, uint32_t* out,
-                             hipStream_t s);
-hipError_t launch_count_live(const uint32_t* planes, const uint32_t* valid, const uint32_t* byz, uint32_t n0,
-                             uint32_t BL, uint32_t L, int honest_only, unsigned long long* out, hipStream_t s);
-// Network census (census.hip): class, count-sum, per-node and count-histogram tallies of local nodes
+// ---- census.hip: network census
+// Network census: class, count-sum, per-node and count-histogram tallies of local nodes
 // [nl0, nl1) in one pass over the A and K planes, read through the deferred count forms (kpend:
 // the engine's array when some tile may hold pending steps or kHiVirt, else nullptr) without
 // writing them back. Outputs (device, zeroed by the caller; nullptr = not wanted, its work is
@@ -528,13 +564,5 @@ struct CensusParams {
   uint32_t bl_div64;       // BL divides 64: a node's lanes sit in one wave
 };
 hipError_t launch_census(CensusParams p, uint32_t nl0, uint32_t nl1, uint32_t blocks, hipStream_t s);
-// Batched poll sets (GetInvsForNextPoll of nodes [nl0, nl0 + n)): the per-node counts, their device
-// scan into offsets (n + 1, u64) and the CSR targets in one stream-ordered sequence; entries at or past
-// cap are not written. offs_out / targets_out may be host-mapped pinned memory (hipHostGetDevicePointer):
-// the fill kernel's stores are coalesced. scratch: poll_sets_scratch_words(n) u64.
-uint64_t poll_sets_scratch_words(uint32_t n);
-hipError_t launch_poll_sets_batch(const uint32_t* planes, const uint32_t* valid, uint32_t BL, uint32_t nl0,
-                                  uint32_t n, uint32_t t0, uint64_t cap, uint64_t* scratch, int64_t* offs_out,
-                                  int32_t* targets_out, hipStream_t s);
 
 }  // namespace avk

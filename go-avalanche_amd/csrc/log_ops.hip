@@ -21,8 +21,6 @@
 //    splitmix64(word)) that the oracle computes the same way
 //    (oracle/avalanche_oracle.c avo_mix64), for full-size parity checks that
 //    do not copy billions of updates to the host.
-// The drop-in RegisterVotes batch groups its votes by lane with the stable
-// radix sort of dev_scan.h (launch_group_votes). No library sort or scan.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -306,24 +304,6 @@ __global__ __launch_bounds__(kEncThreads) void k_bucket_scatter(EncArgs a, const
     locate(flat, p.shards, f, kind, addr, p);
     refs[eoff[k >> 32] + (k & 0xFFFFFFFFull)] = ((uint64_t)kind << 62) | addr;
   }
-}
-
-// Position of the r-th (0-based) set bit of m (r < popcount(m)).
-__device__ __forceinline__ uint32_t nth_set(uint32_t m, uint32_t r) {
-  uint32_t pos = 0;
-#pragma unroll
-  for (uint32_t w = 16; w >= 1; w >>= 1) {
-    const uint32_t low = m & ((1u << w) - 1u);
-    const uint32_t c = (uint32_t)__popc(low);
-    if (r >= c) {
-      r -= c;
-      m >>= w;
-      pos += w;
-    } else {
-      m = low;
-    }
-  }
-  return pos;
 }
 
 struct EmitArgs {
@@ -771,65 +751,6 @@ hipError_t launch_touch(const void* src, uint64_t bytes, uint32_t* sink, hipStre
   if (!n16) return hipSuccess;
   const uint32_t g = (uint32_t)std::min<uint64_t>(4096, (n16 + 255u) / 256u);
   hipLaunchKernelGGL(k_touch, dim3(g), dim3(256), 0, s, static_cast<const u32x4*>(src), n16, sink);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// Drop-in RegisterVotes batch (engine.cpp av_register_votes_batch): group the votes by lane (node,
-// 32-target block) keeping their order inside a lane — the stable radix sort of (lane, position) —
-// then run-length encode the sorted lanes into the (lanes, offs) CSR k_register_votes walks.
-// ---------------------------------------------------------------------------
-namespace {
-struct HeadsIn {
-  const uint32_t* k;
-  __device__ uint64_t operator()(uint64_t i) const { return (i == 0 || k[i] != k[i - 1]) ? 1u : 0u; }
-};
-// run r of the sorted keys: lanes[r] = its key, offs[r] = its first position; offs[n_runs] = n
-__global__ __launch_bounds__(256) void k_rle_write(const uint32_t* ks, const uint64_t* run_of, uint32_t n,
-                                                   uint32_t* lanes, uint32_t* offs, uint32_t* n_runs) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  if (i == 0 || ks[i] != ks[i - 1]) {
-    const uint32_t r = (uint32_t)run_of[i];
-    lanes[r] = ks[i];
-    offs[r] = i;
-  }
-  if (i == n - 1u) {
-    const uint32_t nr = (uint32_t)run_of[n];
-    offs[nr] = n;
-    *n_runs = nr;
-  }
-}
-// entries[2i] = vote index, entries[2i+1] = packed vote (k_register_votes)
-__global__ __launch_bounds__(256) void k_vote_entries(const uint32_t* perm, const uint32_t* vidx, const uint32_t* info,
-                                                      uint32_t n, uint32_t* entries) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t j = perm[i];
-  entries[2u * i] = vidx[j];
-  entries[2u * i + 1u] = info[j];
-}
-}  // namespace
-
-uint64_t group_votes_scratch_words(uint32_t n) {
-  return std::max<uint64_t>(dscan::radix_scratch_words(n), (uint64_t)n + 1u + dscan::scan_scratch_words((uint64_t)n + 1u));
-}
-
-hipError_t launch_group_votes(uint64_t* scratch, const uint32_t* keys, const uint32_t* vidx, const uint32_t* info,
-                              uint32_t n, int key_bits, uint32_t* keys_s, uint32_t* perm_s, uint32_t* keys_t,
-                              uint32_t* perm_t, uint32_t* lanes, uint32_t* offs, uint32_t* n_runs, uint32_t* entries,
-                              hipStream_t s) {
-  if (n == 0) return hipMemsetAsync(n_runs, 0, 4, s);
-  hipError_t e = dscan::launch_radix_sort_pairs(keys, nullptr, n, key_bits, keys_s, perm_s, keys_t, perm_t, scratch, s);
-  if (e != hipSuccess) return e;
-  // run index of every position: exclusive scan of the run heads (run_of[n] = runs)
-  uint64_t* run_of = scratch;
-  if ((e = dscan::launch_scan(HeadsIn{keys_s}, n, run_of, scratch + n + 1u, s)) != hipSuccess) return e;
-  const uint32_t g = (n + 255u) / 256u;
-  hipLaunchKernelGGL(k_rle_write, dim3(g), dim3(256), 0, s, (const uint32_t*)keys_s, (const uint64_t*)run_of, n,
-                     lanes, offs, n_runs);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(k_vote_entries, dim3(g), dim3(256), 0, s, (const uint32_t*)perm_s, vidx, info, n, entries);
   return hipGetLastError();
 }
 

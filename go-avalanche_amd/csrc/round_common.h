@@ -1,5 +1,6 @@
-// Device helpers shared by the round kernels (kernels.hip: per-lane round,
-// capped round, drop-in; round_sweep.hip: the persistent streaming round).
+// Device helpers shared by the round kernels (round_firstgen.hip: per-lane
+// round, capped round; round_sweep.hip: the persistent streaming round;
+// round_node.hip) and by every other kernel that reads the record planes.
 // Philox4x32-10, the bit-sliced VoteRecord step (vote.go:54-75), peer
 // sampling, wave scans, StatusUpdate emission (processor.go:111) and the
 // per-wave counters. Header-only: every translation unit gets its own

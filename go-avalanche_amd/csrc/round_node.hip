@@ -10,7 +10,7 @@
 //    threshold networks, deferred confidence update, the shift registers of
 //    the polled records advanced by k votes at once (round_slots.h);
 //  * otherwise the node is flagged and left untouched; a second launch of the
-//    first version's exact kernel (kernels.hip k_round_capped: per-vote
+//    first version's exact kernel (round_firstgen.hip k_round_capped: per-vote
 //    poll-set re-selection, deletion at 128) processes the flagged nodes only.
 //    Keeping the exact path out of this kernel keeps it at ~66 VGPRs.
 // Same layout, outputs and counters as k_round_capped; V/K move as dwordx4.
@@ -697,33 +697,12 @@ hipError_t launch_node_k(const RoundParams& p, bool replay, hipStream_t s) {
 
 hipError_t launch_replay_node(const RoundParams& p, int k, hipStream_t s) {
   if (!p.node_flags || p.fuse_rounds == 0u || !p.replay) return hipErrorInvalidValue;
-  switch (k) {
-    case 1: return launch_replay_k<1>(p, s);
-    case 2: return launch_replay_k<2>(p, s);
-    case 3: return launch_replay_k<3>(p, s);
-    case 4: return launch_replay_k<4>(p, s);
-    case 5: return launch_replay_k<5>(p, s);
-    case 6: return launch_replay_k<6>(p, s);
-    case 7: return launch_replay_k<7>(p, s);
-    case 8: return launch_replay_k<8>(p, s);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_k<8>(k, [&](auto K) { return launch_replay_k<K()>(p, s); });
 }
 
 hipError_t launch_round_node(const RoundParams& p, int k, bool replay, bool exact_pass, hipStream_t s) {
   if (!p.node_flags) return hipErrorInvalidValue;
-  hipError_t e;
-  switch (k) {
-    case 1: e = launch_node_k<1>(p, replay, s); break;
-    case 2: e = launch_node_k<2>(p, replay, s); break;
-    case 3: e = launch_node_k<3>(p, replay, s); break;
-    case 4: e = launch_node_k<4>(p, replay, s); break;
-    case 5: e = launch_node_k<5>(p, replay, s); break;
-    case 6: e = launch_node_k<6>(p, replay, s); break;
-    case 7: e = launch_node_k<7>(p, replay, s); break;
-    case 8: e = launch_node_k<8>(p, replay, s); break;
-    default: return hipErrorInvalidValue;
-  }
+  const hipError_t e = dispatch_k<8>(k, [&](auto K) { return launch_node_k<K()>(p, replay, s); });
   if (e != hipSuccess || !exact_pass) return e;
   return launch_round(p, k, replay, /*capped=*/true, s);  // the exact pass over the flagged nodes
 }

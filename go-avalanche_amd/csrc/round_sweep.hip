@@ -7,7 +7,7 @@
 // StatusUpdate emission (processor.go:111) and deletion on finalization
 // (:114-116).
 //
-// Same HBM layout, outputs and counters as k_round_fast (kernels.hip); what
+// Same HBM layout, outputs and counters as k_round_fast (round_firstgen.hip); what
 // differs is how the work maps onto CDNA4:
 //  * the Philox peer draw runs once per (node, Philox block) across the
 //    wave's lanes and is handed to the node's lanes with ds_bpermute, instead
@@ -1712,24 +1712,9 @@ hipError_t occupancy_k(bool replay, int* bpc) {
 
 }  // namespace
 
-#define AVK_SWEEP_SWITCH(k, CALL) \
-  switch (k) {                    \
-    case 1: return CALL(1);       \
-    case 2: return CALL(2);       \
-    case 3: return CALL(3);       \
-    case 4: return CALL(4);       \
-    case 5: return CALL(5);       \
-    case 6: return CALL(6);       \
-    case 7: return CALL(7);       \
-    case 8: return CALL(8);       \
-    default: return hipErrorInvalidValue; \
-  }
-
 hipError_t launch_round_sweep(const RoundParams& p, int k, SweepMode mode, uint32_t blocks, hipStream_t s,
                               bool* ref_written) {
-#define AVK_SW(K) launch_sweep_k<K>(p, mode, blocks, s, ref_written)
-  AVK_SWEEP_SWITCH(k, AVK_SW)
-#undef AVK_SW
+  return dispatch_k<8>(k, [&](auto K) { return launch_sweep_k<K()>(p, mode, blocks, s, ref_written); });
 }
 
 hipError_t launch_materialize(const RoundParams& p, bool do_v, bool do_k, hipStream_t s) {
@@ -1748,9 +1733,7 @@ hipError_t round_sweep_occupancy(int k, bool replay, int* blocks_per_cu, int* cu
   if (e != hipSuccess) return e;
   e = hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev);
   if (e != hipSuccess) return e;
-#define AVK_OCC(K) occupancy_k<K>(replay, blocks_per_cu)
-  AVK_SWEEP_SWITCH(k, AVK_OCC)
-#undef AVK_OCC
+  return dispatch_k<8>(k, [&](auto K) { return occupancy_k<K()>(replay, blocks_per_cu); });
 }
 
 }  // namespace avk

@@ -125,7 +125,7 @@ def test_register_votes_batch_vs_oracle(oracle, seed):
 
 def test_register_votes_batch_device_grouping(oracle):
     """Batches of >= 65536 votes are grouped by lane on the device (radix sort
-    of (lane, position) + run-length encode, log_ops.hip launch_group_votes):
+    of (lane, position) + run-length encode, dropin.hip launch_group_votes):
     the same statuses and records as the oracle's RegisterVotes per Response,
     with nodes repeated across the batch (their Responses apply in order)."""
     rng = np.random.default_rng(77)
