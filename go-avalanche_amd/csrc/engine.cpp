@@ -114,6 +114,12 @@ avk::RoundParams round_params(const av_engine* e, const uint32_t* replay) {
 // a round asks for them first. counts: the pending +8 steps of deferred count planes (kernels.h
 // klazy); every path that reads or writes counts other than a klazy round asks for them first.
 int materialize(av_engine* e, bool votes, bool counts) {
+  // preset consider planes (kernels.h c_preset) go with the votes: stored explicitly, in a pass of
+  // their own (no round has run since av_init_records, so nothing else is deferred)
+  if (votes && e->facts.c_preset) {
+    AV_HIP(avk::launch_c_unpreset(e->planes, e->BL, e->L, (uint32_t)(e->t1 - e->t0), e->stream));
+    e->facts.c_unpreset();
+  }
   votes = votes && e->facts.v_stale;
   counts = counts && e->facts.k_pend;
   if (!votes && !counts) return AV_OK;
@@ -227,13 +233,17 @@ int refresh_pref(av_engine* e) {
 
 namespace {
 
+avk::PlanShape plan_shape(const av_engine* e) {
+  return {e->k,      e->BL,         e->N,               e->NL,       e->PS,
+          e->capped, e->peer_world, e->comm != nullptr, e->pub_mode, e->any_nopoll};
+}
+avk::PlanKnobs plan_knobs(const av_engine* e) {
+  return {e->kernel,   e->virtual_votes, e->vv_min_bl,     e->count_lazy,     e->k_hi_virtual,
+          e->ref_rows, e->uni_rows,      e->ablate_gather, e->unsynced_shard, e->quiet_tiles != 0,
+          e->net_quiet != 0, e->count_changed};
+}
 avk::RoundPlan plan_for(const av_engine* e, bool replay) {
-  const avk::PlanShape shape{e->k,       e->BL,         e->N,           e->NL,       e->PS,
-                             e->capped,  e->peer_world, e->comm != nullptr, e->pub_mode, e->any_nopoll};
-  const avk::PlanKnobs knobs{e->kernel,       e->virtual_votes, e->vv_min_bl, e->count_lazy,    e->k_hi_virtual,
-                             e->ref_rows,     e->uni_rows,      e->ablate_gather, e->unsynced_shard,
-                             e->quiet_tiles != 0, e->net_quiet != 0, e->count_changed};
-  return avk::plan_round(e->facts, shape, knobs, replay);
+  return avk::plan_round(e->facts, plan_shape(e), plan_knobs(e), replay);
 }
 
 int round_checks(const av_engine* e, int64_t rounds) {
@@ -379,9 +389,10 @@ int launch_one_round(av_engine* e, const uint32_t* replay) {
   avk::RoundPlan plan = plan_for(e, replay != nullptr);
   AV_CHECK(!plan.unsupported, AV_ERR_UNSUPPORTED,
            "the example responder and av_set_polling need M <= 4096 (uncapped)");
-  AV_TRY(materialize(e, plan.wb_votes, false));  // (two passes, votes first)
+  AV_TRY(materialize(e, plan.wb_votes || plan.wb_cpreset, false));  // (two passes, votes first)
   AV_TRY(materialize(e, false, plan.wb_counts));
   avk::RoundParams p = round_params(e, replay);
+  p.c_preset = e->facts.c_preset ? 1u : 0u;  // (left only before a fresh sweep round: plan.wb_cpreset)
   p.vv = plan.vv ? 1u : 0u;
   p.vv_uniform = plan.vv_uniform ? 1u : 0u;
   p.fresh = plan.fresh ? 1u : 0u;
@@ -647,8 +658,13 @@ int av_init_records(av_engine* e, int32_t init_mode, uint32_t init_param) {
   // every plane is rewritten: nothing deferred survives
   if (e->facts.v_stale) AV_HIP(hipMemsetAsync(e->vstale, 0, (size_t)(e->Lpad / 64) * 4, e->stream));
   if (e->facts.k_pend) AV_HIP(hipMemsetAsync(e->kpend, 0, (size_t)(e->Lpad / 64) * 4, e->stream));
-  e->facts.init(init_mode != AV_INIT_NONE);
+  // the consider planes preset (kernels.h c_preset) where the new records' next sim round would plan
+  // as a fresh sweep round, with this engine's shape and options as they stand
+  const bool created = init_mode != AV_INIT_NONE;
+  const bool preset = created && e->c_preset && avk::plans_c_preset(plan_shape(e), plan_knobs(e));
+  e->facts.init(created, preset);
   avk::InitParams p{};
+  p.c_preset = preset ? 1u : 0u;
   p.planes = e->planes;
   p.pref = e->pref[e->cur];
   p.byz = e->byz;
@@ -790,7 +806,7 @@ int av_materialize(av_engine* e) {
   AV_ENTER(e);
   AV_PEER_CHECK(e);
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (e->facts.v_stale || e->facts.k_pend) AV_TRY(timing_begin(e, &ev0, &ev1));
+  if (e->facts.v_stale || e->facts.k_pend || e->facts.c_preset) AV_TRY(timing_begin(e, &ev0, &ev1));
   AV_TRY(materialize_votes(e));
   return ev0 ? timing_end(e, ev0, ev1) : AV_OK;
 }
@@ -840,6 +856,7 @@ constexpr PlainOption kPlainOptions[] = {
     opt("wave_dense", &av_engine::wave_dense, kReject, 0, 64),  // A/B: dense records per wave (0 off)
     opt("tile_draw", &av_engine::tile_draw, kReject, 0, 1),  // A/B: per-tile shared draws in overflowing runs
     opt("materialize_run", &av_engine::mat_run, kReject, 1, 64),  // A/B: tiles per wave of the write-back
+    opt("c_preset", &av_engine::c_preset),              // A/B: 0 = av_init_records stores C = ~live (kCAll stays in use)
     opt("replay_fuse", &av_engine::replay_fuse, kReject, 0, 4096),  // replay rounds per launch (<= 1: off)
     opt("replay_fast", &av_engine::replay_fast),        // k_replay_fast where the poll set is the first 128 lanes
     opt("dropin_fast", &av_engine::dropin_fast),        // 0: drop-in batches always take the sort-grouped path
@@ -961,7 +978,12 @@ constexpr struct {
     {"pref_uncached", opt_pref_uncached},
     // 0: a round after init reads every plane (A/B only)
     {"fresh", [](av_engine* e, int64_t v) -> int {
-       if (!v) e->facts.option_fresh_off();
+       if (v) return AV_OK;
+       if (e->facts.c_preset) {  // preset consider planes stand only while the records are fresh
+         AV_ENTER(e);
+         AV_TRY(materialize(e, true, false));
+       }
+       e->facts.option_fresh_off();
        return AV_OK;
      }},
     // may only be switched off (it is a proven invariant, not a hint)

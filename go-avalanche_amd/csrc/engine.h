@@ -104,6 +104,9 @@ struct av_engine {
   uint32_t uni_merge = 1;  // option "uni_merge": runs per wave in a round with a uniform input (kernels.h)
   bool k_hi_virtual = true;  // option "k_hi_virtual": the K4..K7 group left unstored while counts are < 16 (kernels.h kHiVirt)
   size_t uni_off = 0;
+  // option "c_preset" (default on, A/B): av_init_records stores the consider planes as all-ones where
+  // the next sim round plans as a fresh sweep round (facts.c_preset, kernels.h c_preset)
+  bool c_preset = true;
 
   int cur = 0;
   static int nxt(int c) { return c == 2 ? 0 : c + 1; }

@@ -280,6 +280,7 @@ int av_read_records(av_engine* e, int64_t n0, int64_t n1, int64_t t0, int64_t t1
   avk::RoundParams p = round_params(e, nullptr);
   p.vv = e->facts.v_stale ? 1u : 0u;
   p.klazy = e->facts.k_pend ? 1u : 0u;
+  p.c_preset = e->facts.c_preset ? 1u : 0u;
   void* buf = nullptr;
   AV_TRY(engine_scratch(e, n * 4, &buf));
   AV_HIP(avk::launch_read_records_virtual(p, (uint32_t)(n0 - e->n0), (uint32_t)(n1 - e->n0), (uint32_t)(t0 - e->t0),

@@ -324,6 +324,11 @@ struct RoundParams {
   uint32_t nq_front;  // option "net_quiet_front": the leaders are the grid's first waves, not every nq_group-th
   uint32_t wave_dense; // k = 8 sweep (A/B option "wave_dense"): a wave with >= wave_dense lanes holding updates
                        // logs every such lane as a dense record (one store branch, no slot-word network); 0 off
+  // Preset consider planes (round_plan.h c_preset): av_init_records stored C0..C7 as all-ones, which
+  // stand for ~real_mask until the fresh sweep round has run. That round leaves the planes of a tile
+  // it would flag kCAll as they are, with no flag (memory already holds what the flag stands for);
+  // k_read_records_v reads C = ~real_mask. Any other reader or writer comes after k_c_unpreset.
+  uint32_t c_preset;
 };
 
 // Dispatch on the runtime k: f(std::integral_constant<int, K>{}) for k = K in [1, MAXK], so that a
@@ -349,8 +354,12 @@ struct InitParams {
   int32_t mode;
   uint32_t param;
   uint32_t pub_mode;    // RoundParams::pub_mode
+  uint32_t c_preset;    // C0..C7 stored as all-ones instead of ~live (RoundParams::c_preset)
 };
 hipError_t launch_init(const InitParams& p, hipStream_t s);
+// k_c_unpreset: C0..C7 = ~real_mask(tn, b) on every lane, the planes k_init_planes stores without
+// c_preset (non-temporal stores: a write-only stream of 32 B per lane)
+hipError_t launch_c_unpreset(uint32_t* planes, uint32_t BL, uint32_t L, uint32_t tn, hipStream_t s);
 hipError_t launch_byz(uint32_t* byz, uint32_t n_nodes, uint64_t seed, uint32_t threshold, hipStream_t s);
 hipError_t launch_read_records(const uint32_t* planes, uint32_t BL, uint32_t nl0, uint32_t nl1,
                                uint32_t tl0, uint32_t tl1, uint32_t* out, hipStream_t s);

@@ -65,7 +65,7 @@ __global__ void k_init_planes(const InitParams p) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     s.V[i] = 0u;
-    s.C[i] = ~live;
+    s.C[i] = p.c_preset ? ~0u : ~live;  // kernels.h c_preset
     s.K[i] = 0u;
   }
   s.K[7] = ~live;
@@ -111,6 +111,23 @@ __global__ void k_byz(uint32_t* byz, uint32_t n_nodes, uint64_t seed, uint32_t t
   byz[wi] = bits;
 }
 }  // namespace
+
+namespace {
+// The consider planes a preset k_init_planes did not store (kernels.h c_preset): consider = 0 on every
+// existing record, 1 past the engine's last target.
+__global__ __launch_bounds__(256) void k_c_unpreset(uint32_t* planes, uint32_t BL, uint32_t L, uint32_t tn) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= L) return;
+  const uint32_t c = ~real_mask(tn, g % BL);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) pst<true>(pw(planes, g, kPC + i), c);
+}
+}  // namespace
+
+hipError_t launch_c_unpreset(uint32_t* planes, uint32_t BL, uint32_t L, uint32_t tn, hipStream_t s) {
+  if (L) hipLaunchKernelGGL(k_c_unpreset, dim3((L + 255) / 256), dim3(256), 0, s, planes, BL, L, tn);
+  return hipGetLastError();
+}
 
 hipError_t launch_byz(uint32_t* byz, uint32_t n_nodes, uint64_t seed, uint32_t threshold, hipStream_t s) {
   const uint32_t words = (n_nodes + 31u) / 32u;
@@ -173,6 +190,10 @@ __global__ __launch_bounds__(256) void k_read_records_v(const RoundParams p, uin
   if (raw & kCAll) {  // consider planes left unstored by the fresh round: all-ones
 #pragma unroll
     for (int q = 0; q < 8; ++q) s.C[q] = ~0u;
+  }
+  if (p.c_preset) {  // stored all-ones by av_init_records, no round since (kernels.h c_preset)
+#pragma unroll
+    for (int q = 0; q < 8; ++q) s.C[q] = ~real_mask(p.tn, b);
   }
   if (st == kVStale) {  // V_i = the vote of round - 1's slot 7 - i (k = 8)
     uint32_t pp[8];

@@ -60,6 +60,9 @@ struct RoundPlan {
   bool exact_pass;  // capped: a count may have reached 120
   // deferred state the round cannot read through, written back before the launch
   bool wb_votes, wb_counts;
+  // the stored consider planes still stand for ~real_mask (RecordFacts::c_preset) and the round is
+  // not the fresh sweep round that makes them true: they are stored explicitly before the launch
+  bool wb_cpreset;
   // reference rows / uniform rows may be used; the caller clears these when no honest reference
   // node exists (ref_pick reads the device)
   bool ref_rows, uni_rows;
@@ -85,6 +88,13 @@ struct RecordFacts {
   // round adds at most k, init/add start at 0, anything else sets it to 127. While it is < 120 no
   // record can finalize in the next round (k <= 8), so the capped path skips its exact pass.
   int count_bound = 127;
+  // every lane's stored consider planes are all-ones and stand for ~real_mask (consider = 0 on every
+  // existing record): av_init_records stored what the fresh sweep round would leave behind (after 8
+  // sim votes every consider bit is 1), so that neither that round nor the first write-back stores
+  // them. Implies fresh. Set by init alone; cleared by after_round and by c_unpreset, which goes with
+  // the pass that stores the planes explicitly. Every other transition that clears fresh (adds,
+  // drop-in votes, writes, option "fresh" = 0) is entered only after that pass.
+  bool c_preset = false;
   bool v_stale = false;  // some tile may be stale
   bool k_pend = false;   // some tile may hold pending steps or flags
   // rflag_ok[b]: the reference-row flags of snapshot buffer b were written by the round that wrote
@@ -111,12 +121,20 @@ struct RecordFacts {
   // Every record starts at count 0 with no considered vote (NewVoteRecord, vote.go:33-35), and a
   // count step needs > 6 considered votes in the 8-vote window (vote.go:58-61): the first 6 votes
   // of a fresh record cannot step it, so after v votes every count is <= v - 6
-  void init(bool records_created) {
+  // preset: the consider planes were stored as all-ones (c_preset; only with records, and only where
+  // the next sim round plans as a fresh sweep round: plans_c_preset below)
+  void init(bool records_created, bool preset = false) {
     snapshot_written();
     warm_all = false;
     count_bound = -6;
     v_stale = k_pend = false;
     fresh = records_created;
+    c_preset = records_created && preset;
+  }
+  // the consider planes were stored explicitly (C = ~real_mask on every lane)
+  void c_unpreset() {
+    c_preset = false;
+    nq_ok = false;
   }
   void add_targets() {
     warm_all = false;
@@ -167,6 +185,7 @@ struct RecordFacts {
     if (p.fresh && p.hivirt) k_pend = true;  // the fresh round flags its tiles kHiVirt
     count_bound = std::min(127, count_bound + p.k);
     fresh = false;
+    c_preset = false;  // a fresh sweep round made the stored planes true; any other was preceded by c_unpreset
     rflag_ok[out_buf] = p.ref_rows && refw;
     uni_ok[out_buf] = p.uni_rows;
     // (every other kind of round: non-klazy, replay, capped, first-generation, an engine with an exchange)
@@ -212,6 +231,7 @@ inline RoundPlan plan_round(const RecordFacts& f, const PlanShape& s, const Plan
   r.exact_pass = f.count_bound >= 120;
   r.wb_votes = !r.vv && f.v_stale;
   r.wb_counts = !r.klazy && !r.kconsume && f.k_pend;
+  r.wb_cpreset = f.c_preset && !r.fresh;
   // reference rows: sweep rounds at k = 8 with a node's lanes inside one wave
   const bool tagged = sweep && s.k == 8 && !replay && !s.has_comm && !o.ablate_gather;
   r.ref_rows = o.ref_rows && tagged && 64 % s.BL == 0;
@@ -223,6 +243,16 @@ inline RoundPlan plan_round(const RecordFacts& f, const PlanShape& s, const Plan
   r.net_quiet_out = o.quiet_tiles && o.net_quiet && r.klazy && sweep && !o.count_changed && s.peer_world <= 1 && !s.has_comm;
   r.net_quiet_in = r.net_quiet_out && f.nq_ok;
   return r;
+}
+
+// av_init_records may preset the consider planes (RecordFacts::c_preset) iff the next sim round of
+// the newly created records would plan as a fresh sweep round: never on capped engines, responder
+// variants, non-polling networks, kernel 1 or ablate_gather.
+inline bool plans_c_preset(const PlanShape& s, const PlanKnobs& o) {
+  RecordFacts f;
+  f.init(true);
+  const RoundPlan r = plan_round(f, s, o, false);
+  return r.fresh && !r.unsupported;
 }
 
 // The sweep grid over `tiles` 64-lane tiles: `blocks` resident workgroups of 4 waves (0 = one wave

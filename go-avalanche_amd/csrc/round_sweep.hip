@@ -679,7 +679,8 @@ __device__ __forceinline__ void process_tile(const RoundParams& p, uint32_t tile
   if constexpr (VVM && !REPLAY && K == 8) {
     // a settled tile's 8 new votes all equal its accepted plane on the polled
     // records: its vote register is A next round (no regather)
-    const uint32_t nv = (virt ? (settled ? kVUniform : kVStale) : 0u) | in.cflag | (cvirt ? kCAll : 0u);
+    // (preset consider planes, kernels.h c_preset: memory already holds what kCAll stands for)
+    const uint32_t nv = (virt ? (settled ? kVUniform : kVStale) : 0u) | in.cflag | (cvirt && !p.c_preset ? kCAll : 0u);
     if (p.vv && lane == 0 && nv != (in.stale | in.cflag)) p.vstale[tile] = nv;
   }
   if constexpr (KL) {
@@ -1611,8 +1612,11 @@ __device__ __forceinline__ void materialize_tile(const RoundParams& p, uint32_t 
   const uint32_t st = raw & kVMask;
   const uint32_t pend = kw & 0xFFu;
   const bool dok = (pend || (kw & kHiVirt)) && x.active;
+  // + 8 * pend reaches the K0..K3 group only through K3, by pend's bit 0, and the carry into K4 then
+  // starts from zero: for an even pend the group is neither loaded nor stored
+  const bool klo = dok && (pend & 1u);
   // ---- loads
-  u32x4 o0, o1, k0, k1;
+  u32x4 o0, o1, k0 = u32x4{0u, 0u, 0u, 0u}, k1;
   if (st == kVUniform) {  // V_i = A on every polled record
     const uint32_t A = tp[1536u + lane];
     o0 = o1 = u32x4{A, A, A, A};
@@ -1628,7 +1632,7 @@ __device__ __forceinline__ void materialize_tile(const RoundParams& p, uint32_t 
   }
   uint32_t vb = 0u;
   if (dok) {
-    k0 = grp[128];
+    if (klo) k0 = grp[128];
     k1 = kw & kHiVirt ? u32x4{0u, 0u, 0u, ~real_mask(p.tn, x.b)} : grp[192];  // kernels.h kHiVirt
     vb = p.valid[x.b];
   }
@@ -1664,7 +1668,7 @@ __device__ __forceinline__ void materialize_tile(const RoundParams& p, uint32_t 
       o2[c] = Kp[c];
       o3[c] = Kp[4 + c];
     }
-    pst4<true>(grp + 128, o2);
+    if (klo) pst4<true>(grp + 128, o2);
     pst4<true>(grp + 192, o3);
   }
 }

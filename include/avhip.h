@@ -410,7 +410,12 @@ int av_sample_peers(av_engine* e, int64_t round, int64_t n0, int64_t n1, int32_t
  * round), "uni_merge" (1: runs per wave in a round with a uniform input),
  * "tile_draw" (0; 1: runs whose nodes overflow the run's peer draw share one
  * draw per tile; exact, measured level), "materialize_run" (1: tiles per wave
- * of the deferred state's write-back), "pref_uncached" (0; 1: snapshot
+ * of the deferred state's write-back), "c_preset" (1: av_init_records stores
+ * the consider planes of new records as all-ones where the next sim round is
+ * the fresh sweep round, which then need not store them, nor the first
+ * write-back; any other use of the records first pays one 32 B per lane pass
+ * that stores them explicitly; takes effect at the next av_init_records;
+ * exact), "pref_uncached" (0; 1: snapshot
  * buffers in uncached memory; exact, measured slower), "peer_mask" (1:
  * need-masked peer pushes; set before the exchange), "push_defer" (1: a
  * wave's pushes queued in LDS and issued after its tiles), "peer_fine" (1),

@@ -3,7 +3,10 @@
 HIP-event time of the write-back after rounds 0..E-1 of a fresh network (E = 16: the end of the
 first timed segment, rounds 5-15; E = 9: the second, rounds 0-8), per option value.
 
-    python tools/wb_probe.py [--workloads c4,c4p,c5] [--ends 16,9] [--runs 1,4,16] [--json out.json]
+    python tools/wb_probe.py [--workloads c4,c4p,c5] [--ends 16,9] [--runs 1,4,16] [--opt name=value ...]
+                             [--json out.json]
+
+`--opt c_preset=0` times the write-back that still stores the consider planes (kernels.h c_preset).
 """
 import argparse
 import json
@@ -41,6 +44,7 @@ def main():
     ap.add_argument("--workloads", default="c4,c4p,c5")
     ap.add_argument("--ends", default="16,9")
     ap.add_argument("--runs", default="1,4,16")
+    ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE", help="engine option set before the runs")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     out = []
@@ -49,12 +53,14 @@ def main():
         e = avhip.Engine(n, m, k=k, seed=0xA7A1A9C4, byz_threshold=byz, log_capacity=0)
         lanes = e.layout_info()["lanes"]
         e.resize_log(2 * lanes, lanes, lanes)
+        for o in args.opt:
+            e.set_option(o.split("=")[0], int(o.split("=")[1]))
         for end in [int(x) for x in args.ends.split(",")]:
             for run in [int(x) for x in args.runs.split(",")]:
                 e.set_option("materialize_run", run)
                 one(e, (init_mode, init_param), end)  # warm-up
                 ms, nl = one(e, (init_mode, init_param), end)
-                row = {"workload": wl, "end": end, "run": run, "ms": ms, "launches": nl}
+                row = {"workload": wl, "end": end, "run": run, "ms": ms, "launches": nl, "opt": args.opt}
                 out.append(row)
                 print(json.dumps(row), flush=True)
         e.close()
