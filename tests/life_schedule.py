@@ -280,6 +280,35 @@ def make_schedule(seed):
                 steps=steps)
 
 
+PEER_REFUSED = frozenset(("register", "register_batch", "add", "write"))  # record writes a peer-push engine refuses
+SHARD_COUNTS = (2, 3, 4, 8)
+PEER_WORLDS = (2, 4, 8)
+
+
+def restrict(sched, drop):
+    """A copy of the schedule without the steps whose op is in `drop`. Observations that were drawn
+    after a dropped step stay, and so do the taken flags of the rounds."""
+    out = dict(sched)
+    out["steps"] = [step for step in sched["steps"] if step["op"] not in drop]
+    return out
+
+
+def target_shards(seed):
+    """The target ranges of a seed's sharded life: 2, 3, 4 or 8 shards (at most one per 32-target
+    block) of whole blocks, balanced to within one block (avhip.sharding.target_shard)."""
+    m = seed_config(seed)[1]
+    blocks = (m + 31) // 32
+    g = min(SHARD_COUNTS[seed % len(SHARD_COUNTS)], blocks)
+    return [(32 * (r * blocks // g), min(32 * ((r + 1) * blocks // g), m)) for r in range(g)]
+
+
+def peer_world(seed):
+    """The number of equal node shards of a seed's peer-group life, or None where N has no such split."""
+    n = seed_config(seed)[0]
+    worlds = [w for w in PEER_WORLDS if n % w == 0]
+    return worlds[seed % len(worlds)] if worlds else None
+
+
 def max_node_votes(step):
     """The most votes one node gets in a drop-in call (what the engine adds to count_bound)."""
     if step["op"] == "register":

@@ -23,23 +23,29 @@ def phase1_steps(sched):
     return out
 
 
+def replay(sched, oracle):
+    """A schedule replayed on the oracle alone: the per-round (rows identical, all valid) and the Life."""
+    life = ls.Life(sched, oracle)
+    state = {}
+
+    def hook(r, sim, valid):
+        pref = sim.pref()
+        state[r] = (bool((pref == pref[0]).all()), bool(valid.all()))
+
+    life.round_hook = hook
+    for i, step in enumerate(sched["steps"]):
+        life.apply(i, step)
+    assert sorted(state) == list(range(sched["rounds"])), sched["seed"]
+    return state, life
+
+
 @pytest.fixture(scope="module")
 def replays(oracle):
     """Every seed's schedule replayed once on the oracle: per seed, the per-round (rows identical, all valid)."""
     out = {}
     for seed in range(ls.N_SEEDS):
         sched = ls.make_schedule(seed)
-        life = ls.Life(sched, oracle)
-        state = {}
-
-        def hook(r, sim, valid, state=state):
-            pref = sim.pref()
-            state[r] = (bool((pref == pref[0]).all()), bool(valid.all()))
-
-        life.round_hook = hook
-        for i, step in enumerate(sched["steps"]):
-            life.apply(i, step)
-        assert sorted(state) == list(range(sched["rounds"])), seed
+        state, life = replay(sched, oracle)
         out[seed] = (sched, state, life)
     return out
 
