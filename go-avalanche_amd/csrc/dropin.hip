@@ -2,7 +2,8 @@
 // one Response or a batch (k_register_votes; k_dropin_resp when every Response's
 // targets ascend, else k_dropin_keys and the stable grouping of the votes by
 // lane, launch_group_votes, with the radix sort and scan of dev_scan.h) and
-// AddTargetToReconcile (k_add_targets). Each launcher sits below its kernels.
+// AddTargetToReconcile: many nodes' lists grouped the same way (k_add_lanes), or one list for every
+// node of a range (k_admit_blocks, k_admit_lanes). Each launcher sits below its kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -224,38 +225,201 @@ hipError_t launch_group_votes(uint64_t* scratch, const uint32_t* keys, const uin
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// AddTargetToReconcile (processor.go:45-58): av_add_targets_batch (k_add_lanes) and av_admit_targets
+// (k_admit_blocks, k_admit_lanes). A record is created iff the target is valid (isWorthyPolling,
+// :46-48) and the node holds no live record of it (K7 set, :50-53).
+// ---------------------------------------------------------------------------
 namespace {
-// AddTargetToReconcile (processor.go:45-58) for a list of targets of one
-// node, applied sequentially by one thread (duplicates return false).
-__global__ void k_add_targets(const AddParams p) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  for (uint32_t i = 0; i < p.n; ++i) {
-    const uint32_t t = p.targets[i];
-    const uint32_t b = t >> 5, m = 1u << (t & 31u);
-    const uint32_t g = p.node_local * p.BL + b;
-    const bool valid = (p.valid[b] & m) != 0u;               // isWorthyPolling (:46-48)
-    const bool exists = (*pw(p.planes, g, kPK + 7) & m) == 0u;  // record present (:50-53)
-    if (!valid || exists) {
-      p.added[i] = 0;
-      continue;
+// the word offsets create_records uses are plane_off's
+static_assert(plane_off(kPV + 5, 7u) == 1u * 256u + 7u * 4u + 1u && plane_off(kPK + 7, 7u) == 3u * 256u + 7u * 4u + 3u &&
+                  plane_off(kPC + 3, 7u) == 1024u + 3u * 64u + 7u && plane_off(kPA, 7u) == 1536u + 7u,
+              "tile layout");
+
+// NewVoteRecord(accepted) (vote.go:33-35) on the records `add` of lane g: their votes, consider and
+// count bits cleared (the V and K groups as four dwordx4, the eight C words), A = acc on them. A whole
+// block is stored without being read. Returns the lane's new A word.
+__device__ __forceinline__ uint32_t create_records(const uint32_t* planes, uint32_t g, uint32_t add, uint32_t acc) {
+  uint32_t* t = tile_of(planes, g);
+  const uint32_t l = g & 63u;
+  u32x4* q = reinterpret_cast<u32x4*>(t) + l;
+  uint32_t* c = t + 1024u + l;
+  uint32_t* a = t + 1536u + l;
+  if (add == ~0u) {
+    const u32x4 z = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) q[i * 64] = z;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) c[i * 64] = 0u;
+    *a = acc;
+    return acc;
+  }
+  const uint32_t keep = ~add;
+  u32x4 v[4];
+  uint32_t cw[8];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) v[i] = q[i * 64];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) cw[i] = c[i * 64];
+  const uint32_t A = (*a & keep) | (acc & add);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    v[i][0] &= keep;
+    v[i][1] &= keep;
+    v[i][2] &= keep;
+    v[i][3] &= keep;
+    q[i * 64] = v[i];
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) c[i * 64] = cw[i] & keep;
+  *a = A;
+  return A;
+}
+
+// One thread per touched lane (launch_group_votes' runs) walks the lane's entries in call order: the
+// first occurrence of a valid, absent target creates its record, every later one returns false. The
+// lane's planes are read and written once, its published word once; a lane that creates nothing
+// stores nothing.
+__global__ void k_add_lanes(const DropInParams p, uint8_t* added) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p.n_blocks) return;
+  const uint32_t g = p.blocks[i];
+  if (g >= p.L) return;  // the run of foreign targets: added stays 0
+  const uint32_t nl = g / p.BL, b = g - nl * p.BL;
+  const uint32_t node = p.n0 + nl;
+  const uint32_t k7 = *pw(p.planes, g, kPK + 7);
+  const uint32_t can = p.valid[b] & k7;
+  uint32_t created = 0u, acc = 0u;
+  for (uint32_t e = p.offs[i]; e < p.offs[i + 1]; ++e) {
+    const uint32_t pos = p.entries[2 * e];
+    const uint32_t meta = p.entries[2 * e + 1];
+    const uint32_t m = 1u << (meta & 31u);
+    const bool ok = (can & ~created & m) != 0u;
+    if (ok) {
+      created |= m;
+      if ((meta >> 5) & 1u) acc |= m;
     }
-    for (int q = 0; q < 8; ++q) {  // NewVoteRecord(t.IsAccepted()) (vote.go:33-35)
-      *pw(p.planes, g, kPV + q) &= ~m;
-      *pw(p.planes, g, kPC + q) &= ~m;
-      *pw(p.planes, g, kPK + q) &= ~m;
+    added[pos] = ok ? 1 : 0;
+  }
+  if (!created) return;
+  const uint32_t A = create_records(p.planes, g, created, acc);
+  p.pref[(size_t)node * p.PS + b] =
+      is_byz(p.byz, node) ? byz_pattern(p.round) : publish_word(A, k7 & ~created, p.pub_mode);
+}
+
+// av_admit_targets, one lane: local node nl adds the records `req` of local block b. Reads the lane's
+// K7 word; a lane with nothing to create stores nothing. Returns the records created.
+__device__ __forceinline__ uint32_t admit_lane(const AdmitParams& p, uint32_t nl, uint32_t b, uint32_t req,
+                                               uint32_t given) {
+  const uint32_t g = nl * p.BL + b;
+  const uint32_t k7 = *pw(p.planes, g, kPK + 7);
+  const uint32_t add = req & p.valid[b] & k7;
+  if (add) {
+    const uint32_t node = p.n0 + nl;
+    const uint32_t acc = p.mode == 5 ? given : init_accept_block(p.seed, p.mode, p.param, node, p.t0 + 32u * b);
+    const uint32_t A = create_records(p.planes, g, add, acc);
+    p.pref[(size_t)node * p.PS + b] =
+        is_byz(p.byz, node) ? byz_pattern(p.round) : publish_word(A, k7 & ~add, p.pub_mode);
+  }
+  return add;
+}
+
+// A wave = 64 consecutive nodes of one touched block (blockIdx.y): the request mask is wave-uniform,
+// and the nodes that created bit i are one ballot and one popcount, kept by lane i over the
+// workgroup's node chunks; the four waves add up in LDS and one atomic instruction per workgroup
+// (32 lanes, the block's 32 consecutive counters: one request for their 128-B line) adds the sums.
+__global__ __launch_bounds__(256) void k_admit_blocks(const AdmitParams p) {
+  __shared__ uint32_t s_cnt[32];
+  const uint32_t j = blockIdx.y;
+  const uint32_t b = p.tblk[j], req = p.treq[j], given = p.tacc[j];
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t mine = 0u;
+  for (uint32_t base = blockIdx.x * 256u; base < p.nn; base += gridDim.x * 256u) {
+    const uint32_t i = base + threadIdx.x;
+    const uint32_t add = i < p.nn ? admit_lane(p, p.nl0 + i, b, req, given) : 0u;
+    if (p.counts) {
+      for (uint32_t r = req; r; r &= r - 1u) {
+        const uint32_t bit = (uint32_t)__builtin_ctz(r);
+        const uint32_t c = (uint32_t)__popcll(__ballot((add >> bit) & 1u));
+        if (lane == bit) mine += c;
+      }
     }
-    uint32_t* a = pw(p.planes, g, kPA);
-    *a = p.accepted[i] ? (*a | m) : (*a & ~m);
-    p.added[i] = 1;
-    p.pref[(size_t)p.node * p.PS + b] = is_byz(p.byz, p.node) ? byz_pattern(p.round)
-                                                               : publish_word(*a, *pw(p.planes, g, kPK + 7), p.pub_mode);
+  }
+  if (!p.counts) return;
+  if (threadIdx.x < 32u) s_cnt[threadIdx.x] = 0u;
+  __syncthreads();
+  if (lane < 32u && mine) atomicAdd(&s_cnt[lane], mine);
+  __syncthreads();
+  if (threadIdx.x < 32u && s_cnt[threadIdx.x]) atomicAdd(p.counts + j * 32u + threadIdx.x, s_cnt[threadIdx.x]);
+}
+
+// Thread v = (node, touched block v % TB): with every block touched, consecutive threads are
+// consecutive lanes and a wave streams whole tiles, as k_init_planes does. The grid's stride is a
+// multiple of TB (launch_admit), so a thread keeps its block: it counts its 32 bits in registers,
+// the workgroup's threads of one block add up in LDS (same block <=> same threadIdx.x % TB), and
+// the sums go to the counters 32 consecutive lanes per block: one request per 128-B counter line
+// (one lane per counter, 32 requests per line and workgroup, cost 0.3 - 0.5 ms on 10^6 x 1000).
+__global__ __launch_bounds__(256) void k_admit_lanes(const AdmitParams p) {
+  __shared__ uint32_t s_cnt[256 * 32];
+  const uint64_t total = (uint64_t)p.nn * p.TB;
+  const uint64_t stride = (uint64_t)gridDim.x * 256u;
+  const uint64_t v0 = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  const uint32_t j = (uint32_t)(v0 % p.TB);
+  const uint32_t b = p.tblk[j], req = p.treq[j], given = p.tacc[j];
+  if (p.counts) {
+    for (uint32_t i = threadIdx.x; i < 256u * 32u; i += 256u) s_cnt[i] = 0u;
+    __syncthreads();
+  }
+  uint32_t cnt[32];
+#pragma unroll
+  for (int i = 0; i < 32; ++i) cnt[i] = 0u;
+  for (uint64_t v = v0; v < total; v += stride) {  // total <= the engine's lanes < 2^32
+    const uint32_t add = admit_lane(p, p.nl0 + (uint32_t)v / p.TB, b, req, given);
+#pragma unroll
+    for (int i = 0; i < 32; ++i) cnt[i] += (add >> i) & 1u;
+  }
+  if (!p.counts) return;
+  const uint32_t slots = min(p.TB, 256u);
+  const uint32_t slot = p.TB <= 256u ? threadIdx.x % p.TB : threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < 32; ++i)
+    if (cnt[i]) atomicAdd(&s_cnt[slot * 32u + i], cnt[i]);
+  __syncthreads();
+  // slot s is the block of the workgroup's thread s (the stride keeps it)
+  const uint32_t j0 = (uint32_t)(((uint64_t)blockIdx.x * 256u) % p.TB);
+  for (uint32_t i = threadIdx.x; i < slots * 32u; i += 256u) {
+    const uint32_t c = s_cnt[i];
+    const uint32_t js = (j0 + (i >> 5)) % p.TB;
+    if (c) atomicAdd(p.counts + js * 32u + (i & 31u), c);
   }
 }
 }  // namespace
 
-hipError_t launch_add_targets(const AddParams& p, hipStream_t s) {
-  if (!p.n) return hipSuccess;
-  hipLaunchKernelGGL(k_add_targets, dim3(1), dim3(64), 0, s, p);
+hipError_t launch_add_lanes(const DropInParams& p, uint8_t* added, hipStream_t s) {
+  if (!p.n_blocks) return hipSuccess;
+  hipLaunchKernelGGL(k_add_lanes, dim3((p.n_blocks + 63) / 64), dim3(64), 0, s, p, added);
+  return hipGetLastError();
+}
+
+hipError_t launch_admit(const AdmitParams& p, bool lane_major, hipStream_t s) {
+  if (!p.nn || !p.TB) return hipSuccess;
+  if (!lane_major) {
+    if (p.TB > 65535u) return hipErrorInvalidValue;
+    const uint32_t gx = std::min<uint32_t>((p.nn + 255u) / 256u, std::max<uint32_t>(1u, 2048u / p.TB));
+    hipLaunchKernelGGL(k_admit_blocks, dim3(gx, p.TB), dim3(256), 0, s, p);
+    return hipGetLastError();
+  }
+  // a grid that does not cover every (node, block) in one pass strides by a multiple of TB
+  const uint64_t need = ((uint64_t)p.nn * p.TB + 255u) / 256u;
+  uint32_t gcd = p.TB, r = 256u;
+  while (r) {
+    const uint32_t t = gcd % r;
+    gcd = r;
+    r = t;
+  }
+  const uint64_t q = p.TB / gcd;
+  const uint64_t cap = (2048u + q - 1u) / q * q;
+  hipLaunchKernelGGL(k_admit_lanes, dim3((uint32_t)std::min(need, cap)), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 

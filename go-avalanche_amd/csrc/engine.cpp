@@ -860,6 +860,7 @@ constexpr PlainOption kPlainOptions[] = {
     opt("replay_fuse", &av_engine::replay_fuse, kReject, 0, 4096),  // replay rounds per launch (<= 1: off)
     opt("replay_fast", &av_engine::replay_fast),        // k_replay_fast where the poll set is the first 128 lanes
     opt("dropin_fast", &av_engine::dropin_fast),        // 0: drop-in batches always take the sort-grouped path
+    opt("admit_map", &av_engine::admit_map, kReject, 0, 2),  // A/B: av_admit_targets' thread mapping (0 = by the touched blocks)
     opt("push_defer", &av_engine::push_defer),          // A/B: 0 = every push stored from the tile loop
     opt("push_store", &av_engine::push_store, kReject, 0, 2),  // A/B: 0 = system scope, 2 = none (invalid)
     opt("census_blocks", &av_engine::census_blocks, kReject, 0, 65536),  // av_census grid (0 = by size)

@@ -295,6 +295,9 @@ struct av_engine {
   avmem::PinnedBuf<void> stage[2];
   avmem::Event stage_ev[2];
   bool dropin_fast = true;
+  // option "admit_map" (A/B and tests): av_admit_targets' thread mapping, 0 = by the touched blocks,
+  // 1 = a wave per 64 nodes of one block, 2 = lane-major (kernels.h launch_admit)
+  uint32_t admit_map = 0;
   // StatusUpdate encoder (log_ops.hip launch_encode_log): error flags and per-pass totals (device)
   avmem::DevBuf<uint32_t> enc_err;
   avmem::DevBuf<uint64_t> enc_tot;  // [4]

@@ -47,52 +47,191 @@ int av_set_valid(av_engine* e, int64_t target, int32_t valid) {
 
 int av_add_targets(av_engine* e, int64_t node, const int64_t* targets, const uint8_t* accepted, int64_t n,
                    uint8_t* added) {
+  const int64_t offs[2] = {0, n};
+  return av_add_targets_batch(e, 1, &node, offs, targets, accepted, added);
+}
+
+// Many Processors' AddTargetToReconcile lists in one call (processor.go:45-58 per entry, in call
+// order). Nothing inside the call changes validity or deletes a record, so the first occurrence of a
+// (node, target) decides and every later one returns false. The host packs each entry into one u32
+// (add_word) in pinned memory; the device forms the lane keys (k_dropin_keys), groups the entries by
+// lane keeping their order (launch_group_votes) and walks each touched lane once (k_add_lanes).
+// Copies: 4 B per entry in, 1 B back.
+int av_add_targets_batch(av_engine* e, int64_t n_req, const int64_t* nodes, const int64_t* offsets,
+                         const int64_t* targets, const uint8_t* accepted, uint8_t* added) {
   if (e) e->facts.snapshot_written();
   AV_ENTER(e);
   AV_TRY(peer_local_write_check(e));
-  AV_CHECK(n >= 0 && (n == 0 || (targets && accepted && added)), AV_ERR_INVALID_ARG, "null argument");
-  AV_CHECK(local_node(e, node), AV_ERR_INVALID_ARG, "node %lld not in this shard", (long long)node);
+  AV_CHECK(n_req >= 0 && (n_req == 0 || (nodes && offsets)), AV_ERR_INVALID_ARG, "null argument");
+  if (n_req == 0) return AV_OK;
+  AV_CHECK(n_req < (1ll << 31), AV_ERR_INVALID_ARG, "too many requests in one call");
+  AV_CHECK(offsets[0] == 0, AV_ERR_INVALID_ARG, "offsets[0] must be 0");
+  for (int64_t i = 0; i < n_req; ++i) {
+    AV_CHECK(offsets[i + 1] >= offsets[i], AV_ERR_INVALID_ARG, "offsets must not decrease");
+    AV_CHECK(local_node(e, nodes[i]), AV_ERR_INVALID_ARG, "node %lld not in this shard", (long long)nodes[i]);
+  }
+  const int64_t n = offsets[n_req];
+  AV_CHECK(n == 0 || (targets && accepted && added), AV_ERR_INVALID_ARG, "null argument");
+  AV_CHECK(n < (1ll << 31), AV_ERR_INVALID_ARG, "too many entries in one call");
+  AV_CHECK(e->t1 - e->t0 <= (int64_t)avk::kDropTl + 1, AV_ERR_UNSUPPORTED, "batched adds need <= 4M local targets");
   AV_TRY(materialize_votes(e));
   e->facts.add_targets();
-  std::vector<uint32_t> tl;
-  std::vector<uint8_t> acc;
-  std::vector<int64_t> pos;
-  for (int64_t i = 0; i < n; ++i) {
-    added[i] = 0;
-    if (!local_target(e, targets[i])) continue;
-    tl.push_back((uint32_t)(targets[i] - e->t0));
-    acc.push_back(accepted[i] ? 1 : 0);
-    pos.push_back(i);
-  }
-  if (tl.empty()) return AV_OK;
-  const size_t m = tl.size();
-  avmem::DevBuf<void> s;
-  AV_HIP(s.alloc(m * 6 + 64));
-  auto* dt = static_cast<uint32_t*>(s.get());
-  auto* da = reinterpret_cast<uint8_t*>(dt + m);
-  auto* dadd = da + m;
-  AV_HIP(hipMemcpyAsync(dt, tl.data(), m * 4, hipMemcpyHostToDevice, e->stream));
-  AV_HIP(hipMemcpyAsync(da, acc.data(), m, hipMemcpyHostToDevice, e->stream));
-  avk::AddParams p{};
+  if (n == 0) return AV_OK;
+  const uint32_t m = (uint32_t)n;
+  // ---- pack (pinned): entries, then the request table, then the result bytes
+  const size_t tab_words = 2 * (size_t)n_req + 1;  // off, node
+  AV_HIP(e->dropin_host.reserve(((size_t)m + tab_words) * 4 + (size_t)m + 64, avmem::Slack::kMiB, hipHostMallocDefault));
+  auto* hpack = static_cast<uint32_t*>(e->dropin_host.get());
+  auto* hoff = hpack + m;
+  auto* hnode = hoff + n_req + 1;
+  auto* hadd = reinterpret_cast<uint8_t*>(hnode + n_req);
+  for (int64_t i = 0; i <= n_req; ++i) hoff[i] = (uint32_t)offsets[i];
+  for (int64_t i = 0; i < n_req; ++i) hnode[i] = (uint32_t)(nodes[i] - e->n0);
+  const int64_t T0 = e->t0, T1 = e->t1;
+  parallel_chunks(n, 1 << 18, [&](int, int64_t a, int64_t b) {
+    for (int64_t v = a; v < b; ++v) {
+      const int64_t tg = targets[v];
+      hpack[v] = avk::add_word(tg - T0, tg >= T0 && tg < T1, accepted[v] != 0);
+    }
+  });
+  // ---- device: packed | off | node | result bytes || keys vidx info keys_s perm_s keys_t perm_t lanes
+  // offs(m+1) nruns entries(2m) | u64 scratch (radix sort, run scan)
+  int key_bits = 1;
+  while (key_bits < 32 && (1ull << key_bits) < (uint64_t)e->L + 1) ++key_bits;  // L = foreign targets
+  const size_t tb = (size_t)avk::group_votes_scratch_words(m) * 8;
+  const size_t head_words = (size_t)m + tab_words + ((size_t)m + 3) / 4;
+  const size_t grp_words = 8 * (size_t)m + ((size_t)m + 1) + 1 + 2 * (size_t)m;
+  void* buf = nullptr;
+  AV_TRY(engine_scratch(e, (head_words + grp_words) * 4 + tb + 512, &buf));
+  auto* w = static_cast<uint32_t*>(buf);
+  uint32_t *dpack = w, *doff = dpack + m, *dnode = doff + n_req + 1;
+  auto* dadd = reinterpret_cast<uint8_t*>(dnode + n_req);
+  AV_HIP(hipMemcpyAsync(dpack, hpack, ((size_t)m + tab_words) * 4, hipMemcpyHostToDevice, e->stream));
+  AV_HIP(hipMemsetAsync(dadd, 0, (size_t)m, e->stream));
+  avk::DropInParams p{};
   p.planes = e->planes;
   p.pref = e->pref[e->cur];
   p.valid = e->valid;
   p.byz = e->byz;
-  p.targets = dt;
-  p.accepted = da;
-  p.added = dadd;
-  p.n = (uint32_t)m;
-  p.node_local = (uint32_t)(node - e->n0);
-  p.node = (uint32_t)node;
+  p.n0 = (uint32_t)e->n0;
   p.BL = e->BL;
   p.PS = e->PS;
+  p.L = e->L;
   p.round = (uint32_t)e->round;
   p.pub_mode = (uint32_t)e->pub_mode;
-  AV_HIP(avk::launch_add_targets(p, e->stream));
-  std::vector<uint8_t> res(m);
-  AV_HIP(hipMemcpyAsync(res.data(), dadd, m, hipMemcpyDeviceToHost, e->stream));
+  p.packed = dpack;
+  p.resp_off = doff;
+  p.resp_node = dnode;
+  p.n_resp = (uint32_t)n_req;
+  uint32_t* g0 = w + head_words;
+  uint32_t *keys = g0, *vidx = keys + m, *info = vidx + m, *keys_s = info + m, *perm_s = keys_s + m,
+           *keys_t = perm_s + m, *perm_t = keys_t + m, *lanes = perm_t + m, *offs = lanes + m, *nruns = offs + m + 1,
+           *ent = nruns + 1;
+  auto* temp = reinterpret_cast<uint64_t*>(((uintptr_t)(ent + 2 * (size_t)m) + 255) & ~(uintptr_t)255);
+  AV_HIP(avk::launch_dropin_keys(p, keys, vidx, info, e->stream));
+  AV_HIP(avk::launch_group_votes(temp, keys, vidx, info, m, key_bits, keys_s, perm_s, keys_t, perm_t, lanes, offs,
+                                 nruns, ent, e->stream));
+  uint32_t nb = 0;
+  AV_HIP(hipMemcpyAsync(&nb, nruns, 4, hipMemcpyDeviceToHost, e->stream));
   AV_HIP(hipStreamSynchronize(e->stream));
-  for (size_t i = 0; i < m; ++i) added[pos[i]] = res[i];
+  p.blocks = lanes;
+  p.offs = offs;
+  p.entries = ent;
+  p.n_blocks = nb;
+  AV_HIP(avk::launch_add_lanes(p, dadd, e->stream));
+  AV_HIP(hipMemcpyAsync(hadd, dadd, (size_t)m, hipMemcpyDeviceToHost, e->stream));
+  AV_HIP(hipStreamSynchronize(e->stream));
+  std::memcpy(added, hadd, (size_t)m);
+  return AV_OK;
+}
+
+// AddTargetToReconcile of a target list by every node of [n0, n1) (main.go:97-103: every node adds a
+// transaction when it appears). The host folds the list into the blocks it touches: per block a
+// request mask, the caller's acceptance mask and, for each requested bit, the list position of its
+// first occurrence (a repeat finds the record: processor.go:50-53). One table upload, one launch, the
+// touched blocks' counters back, one synchronization.
+int av_admit_targets(av_engine* e, int64_t n0, int64_t n1, const int64_t* targets, int64_t n, int32_t init_mode,
+                     uint32_t init_param, const uint8_t* accepted, int64_t* added_nodes) {
+  if (e) e->facts.snapshot_written();
+  AV_ENTER(e);
+  AV_TRY(peer_local_write_check(e));
+  AV_CHECK(n >= 0 && (n == 0 || targets), AV_ERR_INVALID_ARG, "null argument");
+  AV_CHECK(n < (1ll << 31), AV_ERR_INVALID_ARG, "too many targets in one call");
+  AV_CHECK(init_mode >= AV_INIT_REJECTED && init_mode <= AV_INIT_GIVEN, AV_ERR_INVALID_ARG, "bad init_mode");
+  AV_CHECK(init_mode != AV_INIT_GIVEN || accepted, AV_ERR_INVALID_ARG, "AV_INIT_GIVEN needs accepted[]");
+  if (n0 == 0 && n1 == 0) {
+    n0 = e->n0;
+    n1 = e->n1;
+  }
+  AV_CHECK(n0 >= e->n0 && n0 <= n1 && n1 <= e->n1, AV_ERR_INVALID_ARG, "node range outside this engine's shard");
+  AV_TRY(materialize_votes(e));
+  e->facts.add_targets();
+  if (added_nodes) std::fill(added_nodes, added_nodes + n, (int64_t)0);
+  // table: tblk | treq | tacc, TB words each; first[j * 32 + bit]: list position of the bit's first occurrence
+  std::vector<int32_t> slot_of(e->BL, -1);
+  std::vector<uint32_t> tblk, treq, tacc;
+  std::vector<int64_t> first;
+  for (int64_t i = 0; i < n; ++i) {
+    if (!local_target(e, targets[i])) continue;
+    const int64_t tl = targets[i] - e->t0;
+    const uint32_t b = (uint32_t)(tl >> 5), bit = (uint32_t)(tl & 31);
+    if (slot_of[b] < 0) {
+      slot_of[b] = (int32_t)tblk.size();
+      tblk.push_back(b);
+      treq.push_back(0u);
+      tacc.push_back(0u);
+      first.insert(first.end(), 32, (int64_t)-1);
+    }
+    const size_t j = (size_t)slot_of[b];
+    if ((treq[j] >> bit) & 1u) continue;
+    treq[j] |= 1u << bit;
+    if (init_mode == AV_INIT_GIVEN && accepted[i]) tacc[j] |= 1u << bit;
+    first[j * 32 + bit] = i;
+  }
+  const uint32_t TB = (uint32_t)tblk.size();
+  if (!TB || n0 == n1) return AV_OK;
+  std::vector<uint32_t> table;
+  table.reserve(3 * (size_t)TB);
+  table.insert(table.end(), tblk.begin(), tblk.end());
+  table.insert(table.end(), treq.begin(), treq.end());
+  table.insert(table.end(), tacc.begin(), tacc.end());
+  const size_t cnt_words = added_nodes ? (size_t)TB * 32 : 0;
+  void* buf = nullptr;
+  AV_TRY(engine_scratch(e, (3 * (size_t)TB + cnt_words) * 4, &buf));
+  auto* d = static_cast<uint32_t*>(buf);
+  AV_HIP(hipMemcpyAsync(d, table.data(), table.size() * 4, hipMemcpyHostToDevice, e->stream));
+  if (cnt_words) AV_HIP(hipMemsetAsync(d + 3 * (size_t)TB, 0, cnt_words * 4, e->stream));
+  avk::AdmitParams p{};
+  p.planes = e->planes;
+  p.pref = e->pref[e->cur];
+  p.valid = e->valid;
+  p.byz = e->byz;
+  p.tblk = d;
+  p.treq = d + TB;
+  p.tacc = d + 2 * (size_t)TB;
+  p.counts = cnt_words ? d + 3 * (size_t)TB : nullptr;
+  p.seed = e->cfg.seed;
+  p.n0 = (uint32_t)e->n0;
+  p.nl0 = (uint32_t)(n0 - e->n0);
+  p.nn = (uint32_t)(n1 - n0);
+  p.TB = TB;
+  p.BL = e->BL;
+  p.PS = e->PS;
+  p.t0 = (uint32_t)e->t0;
+  p.round = (uint32_t)e->round;
+  p.pub_mode = (uint32_t)e->pub_mode;
+  p.mode = init_mode;
+  p.param = init_param;
+  // the thread mapping (DESIGN.md "Admission"): a wave per 64 nodes of one block pays a pass over every
+  // node's plane lines per touched block, so it is taken for a single touched block only, where both
+  // mappings reach the same words and its counting is the cheaper one; option "admit_map" forces one
+  const bool lane_major = TB > 65535u || (e->admit_map ? e->admit_map == 2u : TB > 1u);
+  AV_HIP(avk::launch_admit(p, lane_major, e->stream));
+  std::vector<uint32_t> counts(cnt_words);
+  if (cnt_words) AV_HIP(hipMemcpyAsync(counts.data(), p.counts, cnt_words * 4, hipMemcpyDeviceToHost, e->stream));
+  AV_HIP(hipStreamSynchronize(e->stream));
+  for (size_t s = 0; s < cnt_words; ++s)
+    if (first[s] >= 0) added_nodes[first[s]] = (int64_t)counts[s];
   return AV_OK;
 }
 

@@ -451,18 +451,40 @@ hipError_t launch_dropin_resp(const DropInParams& p, hipStream_t s);
 // launch_group_votes.
 hipError_t launch_dropin_keys(const DropInParams& p, uint32_t* keys, uint32_t* vidx, uint32_t* info, hipStream_t s);
 
-struct AddParams {
+// AddTargetToReconcile of many nodes' lists (av_add_targets_batch), grouped like the drop-in votes:
+// p.blocks / p.offs / p.entries are launch_group_votes' runs over entries packed by add_word (the
+// accepted bit where a vote has its yes bit); one thread per touched lane walks its run in call
+// order. added[pos] = 1 iff that entry created a record (zeroed by the caller).
+__host__ __device__ inline uint32_t add_word(int64_t tl, bool local, bool accepted) {
+  return (local ? (uint32_t)tl & kDropTl : kDropUnknown) | (accepted ? kDropYes : 0u);
+}
+hipError_t launch_add_lanes(const DropInParams& p, uint8_t* added, hipStream_t s);
+
+// AddTargetToReconcile of a target list by every node of a range (av_admit_targets). The host folds
+// the list into its touched blocks: touched block j is local block tblk[j] with the request mask
+// treq[j] and, for AV_INIT_GIVEN, the acceptance mask tacc[j]. counts (may be null): [TB][32] nodes
+// that created the record of touched block j's bit i (zeroed by the caller).
+struct AdmitParams {
   uint32_t* planes;
   uint32_t* pref;
   const uint32_t* valid;
   const uint32_t* byz;
-  const uint32_t* targets;  // local target index
-  const uint8_t* accepted;
-  uint8_t* added;
-  uint32_t n, node_local, node, BL, PS, round;
-  uint32_t pub_mode;
+  const uint32_t* tblk;
+  const uint32_t* treq;
+  const uint32_t* tacc;
+  uint32_t* counts;
+  uint64_t seed;
+  uint32_t n0;        // first local node (global id)
+  uint32_t nl0, nn;   // the range: local nodes [nl0, nl0 + nn)
+  uint32_t TB;        // touched blocks
+  uint32_t BL, PS, t0, round, pub_mode;
+  int32_t mode;       // AV_INIT_REJECTED .. AV_INIT_GIVEN
+  uint32_t param;
 };
-hipError_t launch_add_targets(const AddParams& p, hipStream_t s);
+// lane_major = false: a wave's 64 lanes are 64 consecutive nodes of one touched block (TB <= 65535);
+// true: consecutive threads walk a node's touched blocks, then the next node's (the record planes'
+// own order when every block is touched).
+hipError_t launch_admit(const AdmitParams& p, bool lane_major, hipStream_t s);
 // Drop-in batch grouping: stable radix sort of (lane key, position) into (keys_s, perm_s) (keys_t,
 // perm_t: the other buffer set), run-length encoding into lanes / offs (n_runs + 1) / *n_runs, and the
 // (vote index, packed vote) entries in grouped order. scratch: group_votes_scratch_words(n) u64.

@@ -20,34 +20,6 @@
 namespace avk {
 
 namespace {
-__device__ __forceinline__ uint32_t init_accept_block(uint64_t seed, int mode, uint32_t param, uint32_t node,
-                                                      uint32_t tb /* first target, multiple of 32 */) {
-  uint32_t a = 0;
-  if (mode == 2) return ~0u;
-  if (mode == 3) {  // Bernoulli: philox(node, t>>2, 0, INIT)[t&3] < param
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      uint32_t x[4];
-      philox(x, seed, node, (tb >> 2) + q, 0u, kDomInit);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a |= (x[i] < param ? 1u : 0u) << (q * 4 + i);
-    }
-  } else if (mode == 4) {  // pairs (2p, 2p+1): coin = philox(node, p>>2, 0, PAIRS)[p&3] >> 31
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      uint32_t x[4];
-      philox(x, seed, node, (tb >> 3) + q, 0u, kDomPairs);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const uint32_t coin = x[i] >> 31;
-        const int pr = q * 4 + i;  // pair index inside the block (0..15)
-        a |= (coin << (2 * pr)) | ((coin ^ 1u) << (2 * pr + 1));
-      }
-    }
-  }
-  return a;
-}
-
 __device__ __forceinline__ uint32_t target_mask(uint32_t tb, uint32_t n_targets) {
   if (tb >= n_targets) return 0u;
   const uint32_t r = n_targets - tb;

@@ -1131,9 +1131,9 @@ __device__ __forceinline__ uint32_t settled_run_uni(const RoundParams& p, uint32
 // materialize in engine.cpp, zeroes every kpend word), so two deferred
 // rounds must follow it; facts.snapshot_written drops uni_ok of all three buffers, so `uniform` is false in
 // the next round and prev_uni in the next two.
-//  * av_register_votes(_batch), av_add_targets, av_write_records: materialize_votes first (pend = 0,
+//  * av_register_votes(_batch), av_add_targets(_batch), av_admit_targets, av_write_records: materialize_votes first (pend = 0,
 //    kPendAllLive gone) and facts.snapshot_written; they republish the rows they change into the current
-//    snapshot (k_register_votes, k_add_targets, refresh_pref), which is pref_out three rounds later:
+//    snapshot (k_register_votes, k_add_lanes, k_admit_blocks / k_admit_lanes, refresh_pref), which is pref_out three rounds later:
 //    (3) holds with "the call that rewrote the records".
 //  * av_set_valid: materialize_votes (pend = 0) and facts.snapshot_written; A and the rows are untouched, and
 //    the new polled set is first seen by the general path (kPendAllLive cleared).
@@ -1169,7 +1169,7 @@ __device__ __forceinline__ uint32_t settled_run_uni(const RoundParams& p, uint32
 // a wave of round r tagging the word that round r still reads would hide round r - 1's tag); a tag
 // from an older round is smaller than p.round (rounds only grow) and never reads as this one.
 // Who may invalidate the induction between two rounds, and where nq_ok (round_plan.h) is cleared:
-//  * every caller of facts.snapshot_written: av_set_valid, av_add_targets, av_register_votes(_batch),
+//  * every caller of facts.snapshot_written: av_set_valid, av_add_targets(_batch), av_admit_targets, av_register_votes(_batch),
 //    av_write_records, av_init_records (facts.init), av_set_option (every option: the run geometry, the
 //    path's own switches), av_set_polling, responder and exchange set-up, the replay launches;
 //  * every write-back (materialize in engine.cpp: av_materialize, and what any reader or writer of

@@ -144,6 +144,10 @@ class Engine {
   // Push Target::IsValid() of every catalogued target whose value changed
   // (isWorthyPolling is evaluated dynamically: processor.go:185-187).
   void SyncValidity();
+  // Every Processor of the engine calls AddTargetToReconcile(t) (main.go:97-103: each node adds a
+  // transaction when it appears): the catalog slot, then one av_admit_targets call. Returns the
+  // Processors that created a record (0: invalid target, catalog full, or every node holds it).
+  int64_t AddTargetToReconcileAll(const Target& t);
   // Batched rounds for every node (the hot path).
   void RunRounds(int32_t rounds);
   int64_t Round() const;

@@ -71,6 +71,17 @@ void Engine::SyncValidity() {
   }
 }
 
+int64_t Engine::AddTargetToReconcileAll(const Target& t) {
+  if (!t.IsValid()) return 0;  // processor.go:46-48
+  const int64_t s = Intern(t);
+  if (s < 0) return 0;  // catalog full: no slot for a new hash
+  SyncValidity();
+  const uint8_t acc = t.IsAccepted() ? 1 : 0;
+  int64_t added = 0;
+  check(av_admit_targets(h_, 0, 0, &s, 1, AV_INIT_GIVEN, 0, &acc, &added));
+  return added;
+}
+
 void Engine::RunRounds(int32_t rounds) {
   SyncValidity();
   check(av_run_rounds(h_, rounds));

@@ -31,6 +31,7 @@ AV_ERR_PEER = -8
 STATUS_INVALID, STATUS_REJECTED, STATUS_ACCEPTED, STATUS_FINALIZED = 0, 1, 2, 3
 PEERS_RANDOM, PEERS_ROUND_ROBIN = 0, 1
 INIT_NONE, INIT_REJECTED, INIT_ACCEPTED, INIT_BERNOULLI, INIT_PAIRS = 0, 1, 2, 3, 4
+INIT_GIVEN = 5  # av_admit_targets only: acceptance from the caller's accepted[]
 ABSENT_WORD = 0xFFFE0000
 FINALIZATION_SCORE = 128
 MAX_ELEMENT_POLL = 4096
@@ -98,6 +99,7 @@ EXPORTED = [
     "av_register_votes_batch", "av_changed_words", "av_materialize", "av_peer_group_serial", "av_peer_sync",
     "av_pushed_words", "av_log_entries", "av_resize_log", "av_fetch_compact", "av_fetch_compact_async",
     "av_fetch_compact_wait", "av_compact_expand", "av_update_round_shift", "av_net_quiet_rounds",
+    "av_add_targets_batch", "av_admit_targets",
 ]
 
 _lib = None
@@ -122,6 +124,8 @@ def lib():
         "av_last_error": (C.c_char_p, []),
         "av_init_records": (i32, [_vp, i32, u32]),
         "av_add_targets": (i32, [_vp, i64, _vp, _vp, i64, _vp]),
+        "av_add_targets_batch": (i32, [_vp, i64, _vp, _vp, _vp, _vp, _vp]),
+        "av_admit_targets": (i32, [_vp, i64, i64, _vp, i64, i32, u32, _vp, _vp]),
         "av_set_valid": (i32, [_vp, i64, i32]),
         "av_register_votes": (i32, [_vp, i64, _vp, _vp, i64, _vp]),
         "av_is_accepted": (i32, [_vp, i64, i64, P(i32)]),
@@ -332,6 +336,43 @@ class Engine:
         out = np.zeros(max(1, t.size), np.uint8)
         _check(lib().av_add_targets(self._h, node, _ptr(t), _ptr(a), t.size, _ptr(out)))
         return out[: t.size].astype(bool)
+
+    def add_targets_batch(self, nodes, offsets, targets, accepted):
+        """Many AddTargetToReconcile lists in one call (av_add_targets_batch): request i = node
+        nodes[i] adding targets offsets[i]..offsets[i+1]-1 in order. Returns np.bool_[total]: the
+        entries that created a record."""
+        nd = np.ascontiguousarray(nodes, np.int64)
+        of = np.ascontiguousarray(offsets, np.int64)
+        t = np.ascontiguousarray(targets, np.int64)
+        a = np.ascontiguousarray(accepted, np.uint8)
+        # the C entry point reads targets/accepted up to offsets[n]: check the lengths here; what it
+        # checks itself (offsets[0], their order, the nodes) is left to it
+        if of.size != nd.size + 1:
+            raise ValueError(f"offsets has {of.size} entries, expected len(nodes) + 1 = {nd.size + 1}")
+        if not (t.size == a.size and t.size >= int(of.max(initial=0))):
+            raise ValueError(f"targets ({t.size}) and accepted ({a.size}) must both hold max(offsets) = {of.max()} entries")
+        out = np.zeros(max(1, t.size), np.uint8)
+        _check(lib().av_add_targets_batch(self._h, nd.size, _ptr(nd), _ptr(of), _ptr(t), _ptr(a), _ptr(out)))
+        return out[: t.size].astype(bool)
+
+    def admit_targets(self, targets, mode, param=0, accepted=None, n0=0, n1=0, count=True):
+        """Every local node of [n0, n1) (0, 0: the whole shard) adds targets, in order
+        (av_admit_targets). mode: INIT_REJECTED / INIT_ACCEPTED / INIT_BERNOULLI / INIT_PAIRS (the
+        acceptance init_records would give, with param) or INIT_GIVEN (accepted[i] for every node).
+        Returns np.int64[n]: the nodes that created a record at each position (count=False: not
+        counted, returns None)."""
+        t = np.ascontiguousarray(targets, np.int64)
+        a = None
+        if accepted is not None:
+            a = np.ascontiguousarray(accepted, np.uint8)
+            if a.size != t.size:
+                raise ValueError(f"accepted has {a.size} entries, targets {t.size}")
+            if a.size == 0:
+                a = np.zeros(1, np.uint8)
+        out = np.zeros(max(1, t.size), np.int64)
+        _check(lib().av_admit_targets(self._h, n0, n1, _ptr(t), t.size, mode, param,
+                                      _ptr(a) if a is not None else None, _ptr(out) if count else None))
+        return out[: t.size] if count else None
 
     def set_valid(self, target, valid):
         _check(lib().av_set_valid(self._h, target, int(bool(valid))))

@@ -11,6 +11,10 @@
  *
  * Reference interfaces replaced (itsdevbear/go-avalanche):
  *   av_add_targets      <- (*Processor).AddTargetToReconcile   processor.go:45-58
+ *   av_add_targets_batch <- AddTargetToReconcile of many           processor.go:45-58
+ *                          Processors in one call
+ *   av_admit_targets    <- every node adding a target when it      processor.go:45-58, main.go:97-103
+ *                          appears
  *   av_register_votes   <- (*Processor).RegisterVotes           processor.go:61-122
  *   av_register_votes_batch <- RegisterVotes of many Responses /  processor.go:61-122, main.go:136
  *                          Processors in one call
@@ -75,6 +79,7 @@ extern "C" {
 #define AV_INIT_ACCEPTED 2  /* ... IsAccepted() = true */
 #define AV_INIT_BERNOULLI 3 /* IsAccepted() = philox(node, t) < init_param */
 #define AV_INIT_PAIRS 4     /* double-spend pairs (2p, 2p+1), complementary per node */
+#define AV_INIT_GIVEN 5     /* acceptance from the caller's accepted[] (av_admit_targets only) */
 
 /* Canonical record word used by av_read_records / av_write_records:
  *   live record : votes | consider << 8 | confidence << 16  (vote.go:25-29,
@@ -137,6 +142,31 @@ int av_init_records(av_engine* e, int32_t init_mode, uint32_t init_param);
  * added[i] = 1 iff a record was created (false if !IsValid or live record). */
 int av_add_targets(av_engine* e, int64_t node, const int64_t* targets, const uint8_t* accepted, int64_t n,
                    uint8_t* added);
+/* AddTargetToReconcile for many Processors in one call: request r is node
+ * nodes[r] adding targets[offsets[r] .. offsets[r+1]) in order, with
+ * accepted[v] per entry; a node may appear several times (its requests apply
+ * in call order). added[v] as for av_add_targets: the first occurrence of a
+ * (node, target) creates the record if the target is valid and absent, every
+ * later one finds it and returns 0. Argument checks and limits are those of
+ * av_register_votes_batch. */
+int av_add_targets_batch(av_engine* e, int64_t n_req, const int64_t* nodes, const int64_t* offsets,
+                         const int64_t* targets, const uint8_t* accepted, uint8_t* added);
+/* Every local node in [n0, n1) (global ids; 0,0 = the whole shard) calls
+ * AddTargetToReconcile(targets[i]) for i = 0..n-1, in order: what every node
+ * does when a transaction appears (main.go:97-103), also for a target whose
+ * records were deleted on finalization (processor.go:114-116; :50-53 tests only
+ * the map). Per (node, target) the result is av_add_targets': a record is
+ * created iff the target is valid and the node holds no live record of it.
+ * Its acceptance: AV_INIT_REJECTED / AV_INIT_ACCEPTED the constant,
+ * AV_INIT_BERNOULLI / AV_INIT_PAIRS the bit av_init_records gives that (node,
+ * target) under init_param, AV_INIT_GIVEN accepted[i] for every node (accepted
+ * is read in that mode only). Targets < 0, >= M or outside this engine's
+ * target shard are skipped; a repeated target finds the record its first
+ * occurrence made. added_nodes (may be NULL): [n], the nodes of [n0, n1) that
+ * created a record at position i (0 for skipped and repeated positions); it
+ * adds across node shards, and exactly one target shard reports a position. */
+int av_admit_targets(av_engine* e, int64_t n0, int64_t n1, const int64_t* targets, int64_t n, int32_t init_mode,
+                     uint32_t init_param, const uint8_t* accepted, int64_t* added_nodes);
 /* Target.IsValid() of a target for every node (isWorthyPolling, processor.go:101).
  * Validity is per target (per Hash), shared by every node of the engine: the
  * reference keeps, per Processor, the Target object it was given
@@ -434,6 +464,8 @@ int av_sample_peers(av_engine* e, int64_t round, int64_t n0, int64_t n1, int32_t
  * settled tests), "k_hi_virtual" (1: the K4..K7 count planes left unstored
  * while every count is < 16), "settled_lean" (1), "replay_fast" (1),
  * "dropin_fast" (1; 0: drop-in batches always take the sort-grouped path),
+ * "admit_map" (0: av_admit_targets' thread mapping by the touched blocks;
+ * 1: a wave per 64 nodes of one block; 2: lane-major; exact),
  * "push_store" (1: plain peer stores; 0: system scope; 2: none, results
  * invalid), "census_blocks" (0: av_census's grid by size).
  * StatusUpdate delivery: "enc_buckets" (2^26: (round, node) buckets per
@@ -472,8 +504,8 @@ int av_comm_init(av_engine* e, int32_t world, int32_t rank, const uint8_t id[128
  * from IsAccepted, processor.go:125-130, of the round-start snapshot), followed
  * by a device-side barrier across the ranks. Collective: every rank must make
  * the same calls. Record writes outside a round (av_add_targets,
- * av_register_votes, av_write_records) return AV_ERR_UNSUPPORTED on such an
- * engine. */
+ * av_add_targets_batch, av_admit_targets, av_register_votes,
+ * av_write_records) return AV_ERR_UNSUPPORTED on such an engine. */
 #define AV_PEER_HANDLE_BYTES 320  /* 4 IPC handles + the device's PCI bus id */
 int av_peer_handles(av_engine* e, uint8_t out[AV_PEER_HANDLE_BYTES]);
 /* handles: world * AV_PEER_HANDLE_BYTES bytes, rank-ordered (this rank's own blob is ignored) */
