@@ -240,7 +240,7 @@ avk::PlanShape plan_shape(const av_engine* e) {
 avk::PlanKnobs plan_knobs(const av_engine* e) {
   return {e->kernel,   e->virtual_votes, e->vv_min_bl,     e->count_lazy,     e->k_hi_virtual,
           e->ref_rows, e->uni_rows,      e->ablate_gather, e->unsynced_shard, e->quiet_tiles != 0,
-          e->net_quiet != 0, e->count_changed};
+          e->net_quiet != 0, e->count_changed, e->calm_tiles != 0};
 }
 avk::RoundPlan plan_for(const av_engine* e, bool replay) {
   return avk::plan_round(e->facts, plan_shape(e), plan_knobs(e), replay);
@@ -397,6 +397,7 @@ int launch_one_round(av_engine* e, const uint32_t* replay) {
   p.vv_uniform = plan.vv_uniform ? 1u : 0u;
   p.fresh = plan.fresh ? 1u : 0u;
   p.klazy = plan.klazy ? 1u : 0u;
+  p.calm = plan.calm ? 1u : 0u;
   p.kconsume = plan.kconsume ? 1u : 0u;
   p.hivirt = plan.hivirt ? 1u : 0u;
   const bool sweep = plan.kernel == avk::RoundKernel::Sweep;
@@ -850,6 +851,7 @@ constexpr PlainOption kPlainOptions[] = {
     opt("uni_merge", &av_engine::uni_merge, kReject, 1, 16),  // runs per wave, uniform-input rounds
     opt("uni_votes", &av_engine::uni_votes),            // uniform input: the reference word as every tile's votes
     opt("quiet_tiles", &av_engine::quiet_tiles),        // A/B: quiescent settled tiles skip the A read and the republish
+    opt("calm_tiles", &av_engine::calm_tiles),          // A/B: 0 = stale tiles with one stray old vote regather (kernels.h calm)
     opt("net_quiet", &av_engine::net_quiet),            // A/B: rounds after a fully quiescent round skip the per-run work
     opt("net_quiet_group", &av_engine::nq_group, kReject, 1, 16),  // runs per leader wave of such a round
     opt("net_quiet_front", &av_engine::nq_front),       // A/B: 0 = every net_quiet_group-th wave leads, not the grid's first

@@ -270,6 +270,7 @@ struct av_engine {
   uint32_t wave_dense = 0;  // option "wave_dense" (kernels.h RoundParams::wave_dense; A/B)
   uint32_t uni_votes = 1;   // option "uni_votes" (kernels.h RoundParams::uni_votes)
   uint32_t quiet_tiles = 1; // option "quiet_tiles" (kernels.h RoundParams::quiet_tiles; 0: every settled tile is walked)
+  uint32_t calm_tiles = 1;  // option "calm_tiles" (kernels.h RoundParams::calm; 0: such tiles regather)
   // network-quiet rounds (kernels.h nq_*): option "net_quiet" (0: every run tests its own tiles) and
   // "net_quiet_group", the runs a leader wave takes (A/B on MI355X, profiles/r09/ab_net_quiet.log)
   uint32_t net_quiet = 1;

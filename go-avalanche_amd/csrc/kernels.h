@@ -74,6 +74,11 @@ __host__ __device__ inline uint32_t real_mask(uint32_t tn, uint32_t b) {  // exi
   return rem >= 32u ? ~0u : ((1u << rem) - 1u);
 }
 constexpr uint32_t kVStale = 1u, kVUniform = 2u, kVMask = 3u, kCAll = 4u;
+// vstale bit 3, outside kVMask and only ever set together with kVStale (RoundParams::calm): V is
+// stale, and every polled record of the tile has at most one of V0..V6 differing from its accepted
+// bit as stored. Whoever masks with kVMask sees a stale tile; the settled tests of the next klazy
+// round (round_sweep.hip) take the tile as a candidate with no regather.
+constexpr uint32_t kVCalm = 8u;
 
 // Division by the (runtime) block count BL without a hardware divide:
 // Granlund-Montgomery round-up magic, exact for every 32-bit n.
@@ -200,6 +205,7 @@ struct RoundParams {
   // | kCAll: the tile's consider planes were left unstored by the fresh round
   // (after 8 sim votes every consider bit of the tile is 1; no record of the
   // tile is live-but-invalid) and read as all-ones until written back.
+  // | kVCalm (with kVStale only): at most one stale vote per polled record disagrees with A (above).
   uint32_t* vstale;
   const uint32_t* pref_prev; // [N_pad][PS] snapshot of round - 1 (read by stale tiles)
   // Peer-push exchange (node-sharded engines, k_round_sweep only):
@@ -309,6 +315,15 @@ struct RoundParams {
   uint32_t quiet_tiles;  // k = 8 warm sweep, single-engine build (option "quiet_tiles", default 1): a settled tile
                          // with two deferred rounds behind it and uniform input snapshots takes its +8 step with
                          // no A-plane read and no republished row (round_sweep.hip "Quiescent tiles")
+  // Calm tiles (k = 8 warm sweep, klazy rounds with stale votes, not the uniform-only form; option
+  // "calm_tiles", default 1; round_plan.h RoundPlan::calm). A general tile that leaves V
+  // unstored and is not settled flags itself kVCalm when, on every polled record, at most one of this
+  // round's slots 1..7 (next round's V6..V0) differs from the round's final accepted bit. If next
+  // round's 8 votes all equal A, every 8-vote window of that round then holds at most one
+  // disagreement: each slot is a conclusive agreeing vote (count + 8, no flip, no update) and the
+  // register afterwards is the 8 new votes = A: a settled tile's outcome, reached with no regather.
+  // 0: the flag is neither set nor taken.
+  uint32_t calm;
   // Network-quiet rounds (k = 8 warm sweep, single-engine build, klazy rounds with quiet_tiles; option
   // "net_quiet", default 1; round_sweep.hip "Network-quiet rounds"). Two device words, used by round
   // parity. nq_out: this round's word; a wave that owns tiles and whose run is not quiescent throughout

@@ -41,6 +41,7 @@ struct PlanKnobs {
   // the network-quiet word (kernels.h nq_*): options "quiet_tiles" and "net_quiet"; count_changed: the
   // sweep's counting build runs (option "count_changed"), which has no quiescent path
   bool quiet_tiles = true, net_quiet = true, count_changed = false;
+  bool calm_tiles = true;  // option "calm_tiles" (kernels.h RoundParams::calm)
 };
 
 struct RoundPlan {
@@ -70,6 +71,9 @@ struct RoundPlan {
   // klazy sweep round of a single engine with quiet_tiles on); net_quiet_in: the word the round before
   // wrote may be trusted (facts.nq_ok)
   bool net_quiet_out, net_quiet_in;
+  // calm tiles (kernels.h calm): a klazy sweep round at k = 8 whose tiles may be left stale (vv, not
+  // the uniform-only form) flags them kVCalm and takes flagged tiles as settled candidates
+  bool calm;
 };
 
 struct RecordFacts {
@@ -242,6 +246,7 @@ inline RoundPlan plan_round(const RecordFacts& f, const PlanShape& s, const Plan
   // round that cannot be uniform (no uniform rows) still maintains it, by tagging it in every wave
   r.net_quiet_out = o.quiet_tiles && o.net_quiet && r.klazy && sweep && !o.count_changed && s.peer_world <= 1 && !s.has_comm;
   r.net_quiet_in = r.net_quiet_out && f.nq_ok;
+  r.calm = o.calm_tiles && r.klazy && r.vv && !r.vv_uniform && s.k == 8 && sweep;
   return r;
 }
 

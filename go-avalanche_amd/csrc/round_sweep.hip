@@ -216,7 +216,8 @@ struct TileIn {
   u32x4 v0, v1, k0, k1;
   uint32_t A, vmask, byzw;
   uint32_t stale;                // wave-uniform: V planes stale, v0/v1 regathered (kernels.h vstale & kVMask)
-  uint32_t cflag;                // wave-uniform: vstale & kCAll (consider planes virtual, all-ones)
+  uint32_t cflag;                // wave-uniform: vstale & kCAll (consider planes virtual, all-ones); and the
+                                 // word's kVCalm bit as stored, so that the tile's new word is compared with it
   uint32_t kw;                   // wave-uniform: kpend[tile] (kernels.h klazy); K planes not loaded if all-live
   uint32_t C[WARM ? 1 : 8];
   uint32_t uref;                 // uniform rows (p.uni_out): ref_node's word of pref_in for the lane's block
@@ -248,6 +249,21 @@ struct WaveDraw {
 
 __device__ __forceinline__ uint32_t meta_of(const WaveDraw& wd, uint32_t tile) {
   return (uint32_t)__builtin_amdgcn_readlane((int)wd.meta, (int)(tile - wd.t0));
+}
+
+// A settled candidate by its meta word (WaveDraw::meta): every live record of the tile is valid
+// (kPendAllLive), and its vote register is uniform (kVUniform), or stale with at most one stray
+// vote per polled record (kVStale | kVCalm, kernels.h calm; `calm` = p.calm).
+__device__ __forceinline__ bool settled_cand(uint32_t m, uint32_t calm) {
+  const uint32_t v = (m >> 8) & (kVMask | kVCalm);
+  return (m & kPendAllLive) && (v == kVUniform || (calm && v == (kVStale | kVCalm)));
+}
+// A calm tile that settled (m: its meta word): its 8 new votes all equal A, so its vote register is
+// uniform from here on. Called by the one lane that owns the tile's words; returns the bytes written.
+__device__ __forceinline__ uint32_t calm_settle(const RoundParams& p, uint32_t tile, uint32_t m) {
+  if (!((m >> 8) & kVCalm)) return 0u;
+  p.vstale[tile] = kVUniform | ((m >> 8) & kCAll);
+  return 4u;
 }
 
 // word at a 32-bit byte offset from a wave-uniform base (SGPR base + VGPR
@@ -292,7 +308,7 @@ __device__ __forceinline__ void load_tile(const RoundParams& p, uint32_t tile, u
   const bool meta = VV && wd && wd->t0 <= tile && tile - wd->t0 < 64u && p.tpw;
   const uint32_t raw = VV && p.vv ? (meta ? (meta_of(*wd, tile) >> 8) & 0xFFu : uni(p.vstale[tile])) : 0u;
   in.stale = raw & kVMask;
-  in.cflag = raw & kCAll;
+  in.cflag = raw & (kCAll | kVCalm);
   in.kw = 0u;
   if constexpr (FRESH) {
     // NewVoteRecords (vote.go:33-35): votes, consider and count all zero; K7
@@ -437,7 +453,8 @@ __device__ __forceinline__ void ref_flag_store(const RoundParams& p, uint32_t la
   }
 }
 
-template <int K, bool REPLAY, bool WARM, int POL, bool VVM = false, bool REF = false, bool CC = true>
+// CALM: the walking warm mode's tiles (kModeWarm), which may flag themselves kVCalm (kernels.h calm).
+template <int K, bool REPLAY, bool WARM, int POL, bool VVM = false, bool REF = false, bool CC = true, bool CALM = false>
 __device__ __forceinline__ void process_tile(const RoundParams& p, uint32_t tile, uint32_t lane,
                                              const TileIn<K, REPLAY, WARM>& in, uint32_t extra_bytes, SweepAcc& acc,
                                              uint32_t uflags = 0u) {
@@ -575,6 +592,22 @@ __device__ __forceinline__ void process_tile(const RoundParams& p, uint32_t tile
       settled = __ballot(agree != P0) == 0ull;
     }
   }
+  // Calm tiles (kernels.h calm): the tile leaves V unstored and is not settled. Next round's V6..V0
+  // are this round's slots 1..7: on the polled records, x_j = "slot j agrees with A", at most one
+  // zero among the 7 (round_slots.h Agg2), one ballot for the tile. The conservative form: a tile
+  // in which any record flips this round is not calm (exact), so the bound is taken here, against
+  // A_in and before the slot network, while the vote words are live anyway (taken after it, it kept
+  // six of them in registers across the network and cost every general tile). A tile holding a
+  // record whose slots 1 and 2 both disagree is out after 4 instructions: every tile of a storm.
+  bool calm_pre = false;
+  if constexpr (CALM && KL && SYM) {
+    if (p.calm && klazy && virt && !settled && __ballot(((ys[8] ^ A) & (ys[9] ^ A) & P0) != 0u) == 0ull) {
+      Agg2 g{~(ys[8] ^ A), ~0u};
+#pragma unroll
+      for (int j = 2; j < 8; ++j) agg_push(g, ~(ys[7 + j] ^ A));
+      calm_pre = __ballot((~g.z1 & P0) != 0u) == 0ull;
+    }
+  }
   if (settled) {
 #pragma unroll
     for (int j = 0; j < K; ++j) E[j] = 0u;
@@ -588,6 +621,9 @@ __device__ __forceinline__ void process_tile(const RoundParams& p, uint32_t tile
   } else {
     round_slots<K, SYM>(ys, ns, low3, nearfin, det, alive, A, E, c, F, applied);
   }
+  // Calm tiles, second half: no record of the tile flipped in the slot network, so the bound taken
+  // against A_in above holds against the round's final A.
+  const bool calm = calm_pre && __ballot((F & P0) != 0u) == 0ull;
   // deferred count planes: every polled record agreed on all 8 votes (no flip,
   // c == 8) -> K stays as stored and the tile's pending +8 steps grow by one
   bool kdefer = false;
@@ -680,7 +716,8 @@ __device__ __forceinline__ void process_tile(const RoundParams& p, uint32_t tile
     // a settled tile's 8 new votes all equal its accepted plane on the polled
     // records: its vote register is A next round (no regather)
     // (preset consider planes, kernels.h c_preset: memory already holds what kCAll stands for)
-    const uint32_t nv = (virt ? (settled ? kVUniform : kVStale) : 0u) | in.cflag | (cvirt && !p.c_preset ? kCAll : 0u);
+    const uint32_t nv = (virt ? (settled ? kVUniform : kVStale) : 0u) | (in.cflag & kCAll) |
+                        (cvirt && !p.c_preset ? kCAll : 0u) | (calm ? kVCalm : 0u);
     if (p.vv && lane == 0 && nv != (in.stale | in.cflag)) p.vstale[tile] = nv;
   }
   if constexpr (KL) {
@@ -745,9 +782,14 @@ __device__ __forceinline__ void process_tile(const RoundParams& p, uint32_t tile
 // more): no flip, no StatusUpdate, no deletion, V stays uniform, A and K
 // unchanged. This reads A, the validity word and the 8 votes and does exactly
 // that; any other tile returns false and takes the general load + step.
+// A stale tile flagged kVCalm (kernels.h calm) is a candidate too, here and in settled_run /
+// settled_run_uni: at most one of its old votes differs from A on any polled record, so with 8 new
+// votes equal to A every window of the round is still a conclusive agreement. It is tested with no
+// regather; when it settles its tile word becomes kVUniform (vst: the word as stored, 4 B written),
+// when it does not it takes the general path as the stale tile it is.
 template <int POL, bool REF, bool CC>
 __device__ __forceinline__ bool settled_tile(const RoundParams& p, uint32_t tile, uint32_t lane, uint32_t kw,
-                                             const WaveDraw& wd, SweepAcc& acc) {
+                                             const WaveDraw& wd, SweepAcc& acc, uint32_t vst) {
   const uint32_t g = tile * 64u + lane;
   const bool active = g < p.L;
   const uint32_t gc = active ? g : p.L - 1u;
@@ -800,6 +842,7 @@ __device__ __forceinline__ bool settled_tile(const RoundParams& p, uint32_t tile
   }
   if (REF && p.rflag_out) ref_flag_store(p, lane, active, b, node, pub, p.pref_in[p.ref_node * p.PS + (active ? b : 0u)]);
   if (lane == 0) p.kpend[tile] = ((kw & 0xFFu) + 1u) | kPendAllLive | (kw & kHiVirt);
+  const uint32_t cbytes = lane == 0 ? calm_settle(p, tile, vst << 8) : 0u;
   acc.applied += 8u * (uint32_t)__popc(P0);
   // process_tile's accounting for this case: 17 plane words + 8 vote words +
   // valid read, minus V (uniform), V store (virtual), K read + store (deferred),
@@ -810,7 +853,7 @@ __device__ __forceinline__ bool settled_tile(const RoundParams& p, uint32_t tile
   acc.lane_bytes += (active ? 40u + (p.count_changed ? 4u : 0u) + rbytes - (gather ? 0u : 32u) +
                                   (REF && p.rflag_out ? 4u + (b == 0u ? 1u : 0u) : 0u)
                             : 0u) +
-                    (lane == 0 ? 8u : 0u);
+                    (lane == 0 ? 8u : 0u) + cbytes;
   return true;
 }
 
@@ -854,7 +897,9 @@ __device__ __forceinline__ uint32_t settled_run(const RoundParams& p, uint32_t l
   uint32_t applied = 0u, bytes = 0u, reread = 0u;  // per lane
   for (uint32_t i = 0; i < ntiles; ++i) {
     const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)wd.meta, (int)i);
-    if ((m & (kPendAllLive | (kVMask << 8))) != (kPendAllLive | (kVUniform << 8))) continue;
+    // (a run holding a Byzantine node leaves its calm tiles to the general path, as settled_run_uni
+    // leaves all of its tiles: existing byte pins of small Byzantine networks rest on their regather)
+    if (!settled_cand(m, byzm ? 0u : p.calm)) continue;
     const uint32_t tile = t0 + i;
     const uint32_t A = __builtin_amdgcn_raw_buffer_load_b32(ta, aoff + i * (kPlanes * 64u * 4u), 0, POL > 0 ? 2 : 0);
     const uint32_t g = tile * 64u + lane;
@@ -915,6 +960,7 @@ __device__ __forceinline__ uint32_t settled_run(const RoundParams& p, uint32_t l
   if (lane < ntiles && ((done >> lane) & 1u)) {
     p.kpend[t0 + lane] = ((wd.meta & 0xFFu) + 1u) | kPendAllLive | (wd.meta & kHiVirt);
     bytes += 8u;  // kpend read (prologue) + written
+    bytes += calm_settle(p, t0 + lane, wd.meta);
   }
   acc.applied += applied;
   acc.lane_bytes += bytes;
@@ -1015,7 +1061,7 @@ __device__ __forceinline__ uint32_t settled_run_uni(const RoundParams& p, uint32
   uint32_t cand = 0u;
   for (uint32_t i = 0; i < ntiles; ++i) {
     const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)meta, (int)i);
-    if ((m & (kPendAllLive | (kVMask << 8))) == (kPendAllLive | (kVUniform << 8))) cand |= 1u << i;
+    if (settled_cand(m, p.calm)) cand |= 1u << i;
   }
   cand &= ~quiet;
   uint32_t Av[kUniRun];
@@ -1056,6 +1102,7 @@ __device__ __forceinline__ uint32_t settled_run_uni(const RoundParams& p, uint32
     if (lane < ntiles && ((done >> lane) & 1u)) {
       p.kpend[t0 + lane] = ((meta & 0xFFu) + 1u) | kPendAllLive | (meta & kHiVirt);
       bytes += 8u;  // kpend read (prologue) + written
+      bytes += calm_settle(p, t0 + lane, meta);
     }
     acc.applied += applied;
     acc.lane_bytes += bytes;
@@ -1092,6 +1139,7 @@ __device__ __forceinline__ uint32_t settled_run_uni(const RoundParams& p, uint32
   if (lane < ntiles && ((done >> lane) & 1u)) {
     p.kpend[t0 + lane] = ((meta & 0xFFu) + 1u) | kPendAllLive | (meta & kHiVirt);
     bytes += 8u;  // kpend read (prologue) + written
+    bytes += calm_settle(p, t0 + lane, meta);
   }
   acc.applied += applied;
   acc.lane_bytes += bytes;
@@ -1109,7 +1157,10 @@ __device__ __forceinline__ uint32_t settled_run_uni(const RoundParams& p, uint32
 //  * its run holds no Byzantine node (settled_run_uni's own gate).
 // Then (1) the reference node's row of pref_prev is one of "every row" of it, so this round's vote
 // word w is last round's w'; (2) the tile deferred in r - 1, which process_tile, settled_run and
-// settled_run_uni grant only when every polled record agreed with all 8 votes and nothing flipped:
+// settled_run_uni grant only when every polled record agreed with all 8 votes and nothing flipped
+// (a calm tile, kernels.h calm, that settles is no exception: all 8 votes equalled A, A is unchanged
+// and the tile deferred; it becomes kVUniform then, with pend as any other tile's, so it reaches the
+// pend >= 2 asked for here two rounds after it first settles, and is no candidate here before):
 // A & P0 == w' & P0 at the end of r - 1, and A has not changed since, so the settled test of round r
 // holds before A is loaded; (3) pref_out is the ring buffer that held the snapshot of round r - 2's
 // input: every row of it is the row's A plane at the start of r - 2 (published by round r - 3, or by
@@ -1345,7 +1396,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == kMo
             // (a run holding a Byzantine node comes back with no tile done)
             if (quiet == all_tiles && uni_done == all_tiles) nq_tag = false;
           }
-          const bool any_stale = __ballot((st & kVMask) == kVStale) != 0ull;
+          // (the tiles the uniform walk settled, calm ones among them, need no regather; a run holds
+          // at most 16 tiles, lane i its tile i: st is 0 past them, uni_done a 32-bit mask)
+          const bool any_stale = __ballot((st & kVMask) == kVStale && lane < 32u && !((uni_done >> lane) & 1u)) != 0ull;
           if (uni_done != all_tiles) {
             wd.pair = any_stale;
             wd.flagok = 0ull;
@@ -1438,14 +1491,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE == kMo
           }
           if (wd.ok && p.settled_fast && p.klazy && p.vv && !lean_ran) {
             const uint32_t m = meta_of(wd, tile);
-            if (((m >> 8) & kVMask) == kVUniform && (m & kPendAllLive) &&
-                settled_tile<POL, REF, CC>(p, tile, lane, m & (kPendAllLive | kHiVirt | 0xFFu), wd, acc))
+            // (calm tiles only in a run with no Byzantine node, as in settled_run)
+            const bool cok = p.calm && ((m >> 8) & kVCalm) &&
+                             __ballot(lane < wd.nn && is_byz(p.byz, p.n0 + wd.nlA + lane)) == 0ull;
+            if (settled_cand(m, cok ? 1u : 0u) &&
+                settled_tile<POL, REF, CC>(p, tile, lane, m & (kPendAllLive | kHiVirt | 0xFFu), wd, acc, m >> 8))
               continue;
           }
         }
         TileIn<K, false, true> in;
         load_tile<K, false, true, POL, false, true, false, CC>(p, tile, lane, in, &wd, uflags);
-        process_tile<K, false, true, POL, true, REF, CC>(p, tile, lane, in, 0u, acc, uflags);
+        process_tile<K, false, true, POL, true, REF, CC, true>(p, tile, lane, in, 0u, acc, uflags);
       } else if constexpr (MODE == kModeFresh) {
         TileIn<K, false, false> in;
         load_tile<K, false, false, POL, false, true, true>(p, tile, lane, in);

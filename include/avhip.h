@@ -454,6 +454,9 @@ int av_sample_peers(av_engine* e, int64_t round, int64_t n0, int64_t n1, int32_t
  * "quiet_tiles" (1: a settled tile with two deferred rounds behind it and two
  * uniform input snapshots takes its count step with no A-plane read and no
  * republished row; engines without an exchange; exact),
+ * "calm_tiles" (1: a tile whose stale vote register holds at most one vote
+ * per record that differs from the accepted bit settles on its 8 new votes
+ * with no regather; 0: it regathers; exact),
  * "net_quiet" (1: a round after one in which every tile was quiescent, with
  * nothing written in between, adds the count step to the tile words alone:
  * a leader wave takes "net_quiet_group" runs (16; 1..16) and the other waves
