@@ -866,6 +866,8 @@ constexpr PlainOption kPlainOptions[] = {
     opt("push_defer", &av_engine::push_defer),          // A/B: 0 = every push stored from the tile loop
     opt("push_store", &av_engine::push_store, kReject, 0, 2),  // A/B: 0 = system scope, 2 = none (invalid)
     opt("census_blocks", &av_engine::census_blocks, kReject, 0, 65536),  // av_census grid (0 = by size)
+    opt("catalog_blocks", &av_engine::catalog_blocks, kReject, 0, 65535),  // hash lookup grid (0 = by size)
+    opt("catalog_lds", &av_engine::catalog_lds),        // A/B: 0 = the hash table probed in global memory at any size
     opt("copy_blocks", &av_engine::copy_blocks, kReject, 0, 4096),  // stream copy kernel (0 = runtime copy)
     opt("enc_buckets", &av_engine::enc_buckets, kReject, 1, 1ll << 30),  // buckets per encoder pass
     opt("count_changed", &av_engine::count_changed),    // diagnostics: count changed published words in every sweep round

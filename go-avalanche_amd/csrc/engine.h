@@ -322,6 +322,15 @@ struct av_engine {
   size_t cdev_hwm = 0, chost_hwm = 0;
   // batched poll sets (av_get_invs_batch): host-mapped pinned output the fill kernel writes
   avmem::PinnedBuf<void> invs_host;
+  // the Hash catalog over [t0, t1) (catalog.h; set up by the first call that needs it, so an engine
+  // that never uses it pays nothing) and the device copy of its table image, brought up to date by
+  // catalog_sync before a device lookup. cat_group: the grouping scratch of a hashed vote batch that
+  // turns out to need the general path (the engine's scratch holds the batch by then).
+  avcat::Catalog cat;
+  avmem::DevBuf<avcat::Entry> cat_dev;
+  avmem::DevBuf<uint32_t> cat_group;
+  uint32_t catalog_blocks = 0;  // option "catalog_blocks": workgroups of the lookup kernel (0 = by size)
+  bool catalog_lds = true;      // option "catalog_lds" (A/B and tests; 0: tables of any size probed in global memory)
 
   size_t round_replay_words() const { return avk::replay_words(Lpad, k); }
 };
@@ -356,6 +365,15 @@ int realloc_pref(av_engine* e, unsigned flags);
 
 // ---- engine_log.cpp
 int relayout_log_if_empty(av_engine* e);
+
+// ---- engine_catalog.cpp
+// The device copy of the catalog's table image equals the host image (entry patches, or the whole
+// image after a rebuild); the stream is synchronized, so the host image may change again at once.
+int catalog_sync(av_engine* e);
+// hashes[0 .. n) looked up on the device (dh: their 16-byte-aligned device copy) into packed words
+// (dropin_word; errs / resp_off / unordered as CatalogPackParams); enqueued on the engine's stream.
+int catalog_pack(av_engine* e, const int64_t* dh, const uint32_t* derr, const uint32_t* dresp_off, uint32_t n_resp,
+                 uint32_t n, uint32_t* dpacked, uint32_t* dunordered);
 
 // ---- defined here
 // Host work of the drop-in path (packing the caller's votes, expanding the

@@ -241,6 +241,134 @@ int av_register_votes(av_engine* e, int64_t node, const int64_t* targets, const 
   return av_register_votes_batch(e, 1, &node, offs, targets, errs, status_out);
 }
 
+}  // extern "C"
+
+namespace {
+
+// What av_register_votes_batch and av_register_votes_hashed check and derive from the caller's
+// Response table before any vote is looked at (n_resp > 0).
+struct RespTable {
+  int64_t n = 0;               // votes
+  int64_t max_node_votes = 0;  // at most one confidence step per vote: the most votes one node gets
+  // the Responses grouped by node, in call order inside a group (fast path)
+  std::vector<uint32_t> order, grp_off;
+  uint32_t n_groups = 0;
+};
+
+int resp_table(av_engine* e, int64_t n_resp, const int64_t* nodes, const int64_t* offsets, const void* votes,
+               const uint32_t* errs, const int32_t* status_out, RespTable& t) {
+  AV_CHECK(n_resp < (1ll << 31), AV_ERR_INVALID_ARG, "too many Responses in one call");
+  AV_CHECK(offsets[0] == 0, AV_ERR_INVALID_ARG, "offsets[0] must be 0");
+  for (int64_t i = 0; i < n_resp; ++i) {
+    AV_CHECK(offsets[i + 1] >= offsets[i], AV_ERR_INVALID_ARG, "offsets must not decrease");
+    AV_CHECK(local_node(e, nodes[i]), AV_ERR_INVALID_ARG, "node %lld not in this shard", (long long)nodes[i]);
+  }
+  const int64_t n = offsets[n_resp];
+  AV_CHECK(n == 0 || (votes && errs && status_out), AV_ERR_INVALID_ARG, "null argument");
+  AV_CHECK(n < (1ll << 31), AV_ERR_INVALID_ARG, "too many votes in one call");
+  AV_CHECK(e->t1 - e->t0 <= (int64_t)avk::kDropTl + 1, AV_ERR_UNSUPPORTED, "drop-in votes need <= 4M local targets");
+  AV_TRY(materialize_votes(e));
+  t.n = n;
+  t.order.resize((size_t)n_resp);
+  std::vector<std::pair<int64_t, uint32_t>> nn((size_t)n_resp);
+  for (int64_t i = 0; i < n_resp; ++i) nn[(size_t)i] = {nodes[i], (uint32_t)i};
+  std::sort(nn.begin(), nn.end());  // (node, Response index): call order inside a node
+  for (size_t i = 0; i < nn.size();) {
+    int64_t c = 0;
+    size_t j = i;
+    t.grp_off.push_back((uint32_t)i);
+    for (; j < nn.size() && nn[j].first == nn[i].first; ++j) {
+      c += offsets[nn[j].second + 1] - offsets[nn[j].second];
+      t.order[j] = nn[j].second;
+    }
+    t.max_node_votes = std::max(t.max_node_votes, c);
+    i = j;
+  }
+  t.grp_off.push_back((uint32_t)n_resp);
+  t.n_groups = (uint32_t)t.grp_off.size() - 1u;
+  return AV_OK;
+}
+
+// words of the Response table on the device: off (n_resp + 1), node, order, grp_off (n_groups + 1)
+size_t resp_table_words(int64_t n_resp, const RespTable& t) {
+  return 2 * (size_t)n_resp + 1 + (size_t)n_resp + t.n_groups + 1;
+}
+
+void fill_resp_table(const av_engine* e, int64_t n_resp, const int64_t* nodes, const int64_t* offsets,
+                     const RespTable& t, uint32_t* hoff) {
+  auto* hnode = hoff + n_resp + 1;
+  auto* horder = hnode + n_resp;
+  auto* hgrp = horder + n_resp;
+  for (int64_t i = 0; i <= n_resp; ++i) hoff[i] = (uint32_t)offsets[i];
+  for (int64_t i = 0; i < n_resp; ++i) hnode[i] = (uint32_t)(nodes[i] - e->n0);
+  std::memcpy(horder, t.order.data(), (size_t)n_resp * 4);
+  std::memcpy(hgrp, t.grp_off.data(), ((size_t)t.n_groups + 1) * 4);
+}
+
+// words of the general path's grouping scratch for m votes, and its radix / scan bytes
+size_t group_words(uint32_t m) { return 8 * (size_t)m + ((size_t)m + 1) + 1 + 2 * (size_t)m; }
+
+// The packed votes (dpack[m], dropin_word) and the Response table (doff: fill_resp_table's layout)
+// are on the device, the statuses dstat[m] preset to -1: apply them by the fast path (every
+// Response fit for k_dropin_resp) or by the general one (grp: group_words(m) words, then 256 bytes
+// of slack and group_votes_scratch_words(m) u64), copy the statuses to hstat (pinned) and widen them.
+int apply_packed_votes(av_engine* e, const RespTable& t, int64_t n_resp, uint32_t* dpack, uint32_t* doff,
+                       int8_t* dstat, bool fast, uint32_t* grp, int8_t* hstat, int32_t* status_out) {
+  const uint32_t m = (uint32_t)t.n;
+  uint32_t *dnode = doff + n_resp + 1, *dorder = dnode + n_resp, *dgrp = dorder + n_resp;
+  avk::DropInParams p{};
+  p.planes = e->planes;
+  p.pref = e->pref[e->cur];
+  p.valid = e->valid;
+  p.byz = e->byz;
+  p.status_out = dstat;
+  p.n0 = (uint32_t)e->n0;
+  p.BL = e->BL;
+  p.PS = e->PS;
+  p.L = e->L;
+  p.round = (uint32_t)e->round;
+  p.pub_mode = (uint32_t)e->pub_mode;
+  p.packed = dpack;
+  p.resp_off = doff;
+  p.resp_node = dnode;
+  p.n_resp = (uint32_t)n_resp;
+  p.order = dorder;
+  p.grp_off = dgrp;
+  p.n_groups = t.n_groups;
+  if (fast) {
+    AV_HIP(avk::launch_dropin_resp(p, e->stream));
+  } else {
+    int key_bits = 1;
+    const uint64_t keys_total = (uint64_t)e->L + 1;  // L = unknown targets
+    while (key_bits < 32 && (1ull << key_bits) < keys_total) ++key_bits;
+    uint32_t *keys = grp, *vidx = keys + m, *info = vidx + m, *keys_s = info + m, *perm_s = keys_s + m,
+             *keys_t = perm_s + m, *perm_t = keys_t + m, *lanes = perm_t + m, *offs = lanes + m,
+             *nruns = offs + m + 1, *ent = nruns + 1;
+    auto* temp = reinterpret_cast<uint64_t*>(((uintptr_t)(ent + 2 * (size_t)m) + 255) & ~(uintptr_t)255);
+    AV_HIP(avk::launch_dropin_keys(p, keys, vidx, info, e->stream));
+    AV_HIP(avk::launch_group_votes(temp, keys, vidx, info, m, key_bits, keys_s, perm_s, keys_t, perm_t, lanes, offs,
+                                   nruns, ent, e->stream));
+    uint32_t nb = 0;
+    AV_HIP(hipMemcpyAsync(&nb, nruns, 4, hipMemcpyDeviceToHost, e->stream));
+    AV_HIP(hipStreamSynchronize(e->stream));
+    p.blocks = lanes;
+    p.offs = offs;
+    p.entries = ent;
+    p.n_blocks = nb;
+    AV_HIP(avk::launch_register_votes(p, e->stream));
+  }
+  AV_HIP(hipMemcpyAsync(hstat, dstat, (size_t)m, hipMemcpyDeviceToHost, e->stream));
+  AV_HIP(hipStreamSynchronize(e->stream));
+  parallel_chunks(t.n, 1 << 20, [&](int, int64_t a, int64_t b) {
+    for (int64_t i = a; i < b; ++i) status_out[i] = hstat[i];
+  });
+  return AV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 // Many Responses in one call (processor.go:61-122 for each, in order). The
 // host packs each vote into one u32 (target's local index, unknown-hash, yes
 // and considered bits: dropin_word) in pinned memory, in parallel, and checks
@@ -263,58 +391,22 @@ int av_register_votes_batch(av_engine* e, int64_t n_resp, const int64_t* nodes, 
   AV_TRY(peer_local_write_check(e));
   AV_CHECK(n_resp >= 0 && (n_resp == 0 || (nodes && offsets)), AV_ERR_INVALID_ARG, "null argument");
   if (n_resp == 0) return AV_OK;
-  AV_CHECK(n_resp < (1ll << 31), AV_ERR_INVALID_ARG, "too many Responses in one call");
-  AV_CHECK(offsets[0] == 0, AV_ERR_INVALID_ARG, "offsets[0] must be 0");
-  for (int64_t i = 0; i < n_resp; ++i) {
-    AV_CHECK(offsets[i + 1] >= offsets[i], AV_ERR_INVALID_ARG, "offsets must not decrease");
-    AV_CHECK(local_node(e, nodes[i]), AV_ERR_INVALID_ARG, "node %lld not in this shard", (long long)nodes[i]);
-  }
-  const int64_t n = offsets[n_resp];
-  AV_CHECK(n == 0 || (targets && errs && status_out), AV_ERR_INVALID_ARG, "null argument");
-  AV_CHECK(n < (1ll << 31), AV_ERR_INVALID_ARG, "too many votes in one call");
-  AV_CHECK(e->t1 - e->t0 <= (int64_t)avk::kDropTl + 1, AV_ERR_UNSUPPORTED, "drop-in votes need <= 4M local targets");
-  AV_TRY(materialize_votes(e));
-  // at most one confidence step per vote: bound by the most votes one node gets; the Responses
-  // grouped by node, in call order inside a group (fast path)
-  int64_t max_node_votes = 0;
-  std::vector<uint32_t> order((size_t)n_resp), grp_off;
-  {
-    std::vector<std::pair<int64_t, uint32_t>> nn((size_t)n_resp);
-    for (int64_t i = 0; i < n_resp; ++i) nn[(size_t)i] = {nodes[i], (uint32_t)i};
-    std::sort(nn.begin(), nn.end());  // (node, Response index): call order inside a node
-    for (size_t i = 0; i < nn.size();) {
-      int64_t c = 0;
-      size_t j = i;
-      grp_off.push_back((uint32_t)i);
-      for (; j < nn.size() && nn[j].first == nn[i].first; ++j) {
-        c += offsets[nn[j].second + 1] - offsets[nn[j].second];
-        order[j] = nn[j].second;
-      }
-      max_node_votes = std::max(max_node_votes, c);
-      i = j;
-    }
-    grp_off.push_back((uint32_t)n_resp);
-  }
-  const uint32_t n_groups = (uint32_t)grp_off.size() - 1u;
+  RespTable rt;
+  AV_TRY(resp_table(e, n_resp, nodes, offsets, targets, errs, status_out, rt));
+  const int64_t n = rt.n, max_node_votes = rt.max_node_votes;
   if (n == 0) {
     e->facts.dropin_votes(max_node_votes, false);
     return AV_OK;
   }
   // ---- pack (pinned): votes, then the Response table
-  const size_t tab_words = 2 * (size_t)n_resp + 1 + (size_t)n_resp + n_groups + 1;  // off, node, order, grp_off
+  const size_t tab_words = resp_table_words(n_resp, rt);
   const size_t hb = (size_t)n * 5 + tab_words * 4 + 64;
   // (pinned host staging, grown on demand and kept by the engine)
   AV_HIP(e->dropin_host.reserve(hb, avmem::Slack::kMiB, hipHostMallocDefault));
   auto* hpack = static_cast<uint32_t*>(e->dropin_host.get());
   auto* hoff = hpack + n;
-  auto* hnode = hoff + n_resp + 1;
-  auto* horder = hnode + n_resp;
-  auto* hgrp = horder + n_resp;
-  auto* hstat = reinterpret_cast<int8_t*>(hgrp + n_groups + 1);
-  for (int64_t i = 0; i <= n_resp; ++i) hoff[i] = (uint32_t)offsets[i];
-  for (int64_t i = 0; i < n_resp; ++i) hnode[i] = (uint32_t)(nodes[i] - e->n0);
-  std::memcpy(horder, order.data(), (size_t)n_resp * 4);
-  std::memcpy(hgrp, grp_off.data(), ((size_t)n_groups + 1) * 4);
+  auto* hstat = reinterpret_cast<int8_t*>(hoff + tab_words);
+  fill_resp_table(e, n_resp, nodes, offsets, rt, hoff);
   std::vector<uint8_t> asc_t(64, 1), neutral_t(64, 0);
   const int64_t T0 = e->t0, T1 = e->t1;
   parallel_chunks(n_resp, std::max<int64_t>(1, n_resp * (1 << 18) / std::max<int64_t>(1, n)),
@@ -340,71 +432,95 @@ int av_register_votes_batch(av_engine* e, int64_t n_resp, const int64_t* nodes, 
   e->facts.dropin_votes(max_node_votes, neutral);
   const bool fast = ascending && e->dropin_fast;
   // ---- device: packed votes + Response table + byte statuses (+ grouping scratch)
-  size_t tb = 0;
-  int key_bits = 1;
   const uint32_t m = (uint32_t)n;
-  if (!fast) {
-    const uint64_t keys_total = (uint64_t)e->L + 1;  // L = unknown targets
-    while (key_bits < 32 && (1ull << key_bits) < keys_total) ++key_bits;
-    tb = (size_t)avk::group_votes_scratch_words(m) * 8;
-  }
+  const size_t tb = fast ? 0 : (size_t)avk::group_votes_scratch_words(m) * 8;
   // packed | off | node | status bytes || keys vidx info keys_s perm_s keys_t perm_t lanes offs(m+1) nruns
   // entries(2m) | u64 scratch (radix sort, run scan)
   const size_t head_words = (size_t)m + tab_words + ((size_t)m + 3) / 4;
-  const size_t grp_words = fast ? 0 : 8 * (size_t)m + ((size_t)m + 1) + 1 + 2 * (size_t)m;
+  const size_t grp_words = fast ? 0 : group_words(m);
   void* buf = nullptr;
   AV_TRY(engine_scratch(e, (head_words + grp_words) * 4 + tb + 512, &buf));
   auto* w = static_cast<uint32_t*>(buf);
-  uint32_t *dpack = w, *doff = dpack + m, *dnode = doff + n_resp + 1, *dorder = dnode + n_resp,
-           *dgrp = dorder + n_resp;
-  auto* dstat = reinterpret_cast<int8_t*>(dgrp + n_groups + 1);
+  uint32_t *dpack = w, *doff = dpack + m;
+  auto* dstat = reinterpret_cast<int8_t*>(doff + tab_words);
   AV_HIP(hipMemcpyAsync(dpack, hpack, ((size_t)m + tab_words) * 4, hipMemcpyHostToDevice, e->stream));
   AV_HIP(hipMemsetAsync(dstat, 0xFF, (size_t)m, e->stream));
-  avk::DropInParams p{};
-  p.planes = e->planes;
-  p.pref = e->pref[e->cur];
-  p.valid = e->valid;
-  p.byz = e->byz;
-  p.status_out = dstat;
-  p.n0 = (uint32_t)e->n0;
-  p.BL = e->BL;
-  p.PS = e->PS;
-  p.L = e->L;
-  p.round = (uint32_t)e->round;
-  p.pub_mode = (uint32_t)e->pub_mode;
-  p.packed = dpack;
-  p.resp_off = doff;
-  p.resp_node = dnode;
-  p.n_resp = (uint32_t)n_resp;
-  p.order = dorder;
-  p.grp_off = dgrp;
-  p.n_groups = n_groups;
-  if (fast) {
-    AV_HIP(avk::launch_dropin_resp(p, e->stream));
-  } else {
-    uint32_t* g0 = w + head_words;
-    uint32_t *keys = g0, *vidx = keys + m, *info = vidx + m, *keys_s = info + m, *perm_s = keys_s + m,
-             *keys_t = perm_s + m, *perm_t = keys_t + m, *lanes = perm_t + m, *offs = lanes + m,
-             *nruns = offs + m + 1, *ent = nruns + 1;
-    auto* temp = reinterpret_cast<uint64_t*>(((uintptr_t)(ent + 2 * (size_t)m) + 255) & ~(uintptr_t)255);
-    AV_HIP(avk::launch_dropin_keys(p, keys, vidx, info, e->stream));
-    AV_HIP(avk::launch_group_votes(temp, keys, vidx, info, m, key_bits, keys_s, perm_s, keys_t, perm_t, lanes, offs,
-                                   nruns, ent, e->stream));
-    uint32_t nb = 0;
-    AV_HIP(hipMemcpyAsync(&nb, nruns, 4, hipMemcpyDeviceToHost, e->stream));
-    AV_HIP(hipStreamSynchronize(e->stream));
-    p.blocks = lanes;
-    p.offs = offs;
-    p.entries = ent;
-    p.n_blocks = nb;
-    AV_HIP(avk::launch_register_votes(p, e->stream));
+  return apply_packed_votes(e, rt, n_resp, dpack, doff, dstat, fast, w + head_words, hstat, status_out);
+}
+
+// av_register_votes_batch with the caller's hashes in place of slots. The host copies the 8-byte
+// hashes and the err classes into pinned memory and looks nothing up: the device probes its copy of
+// the catalog's table per vote and writes the packed votes (catalog.hip k_catalog_pack) that both
+// apply paths of the slot call consume. Whether the fast path may run (every Response's slots
+// ascending) is the kernel's finding too, read back before the apply is enqueued. What the round
+// plan needs is derived from the errs exactly as the slot call derives it.
+// Copies: 12 B per vote in, 1 B back.
+int av_register_votes_hashed(av_engine* e, int64_t n_resp, const int64_t* nodes, const int64_t* offsets,
+                             const int64_t* hashes, const uint32_t* errs, int32_t* status_out) {
+  if (e) e->facts.snapshot_written();
+  AV_ENTER(e);
+  AV_TRY(peer_local_write_check(e));
+  AV_CHECK(n_resp >= 0 && (n_resp == 0 || (nodes && offsets)), AV_ERR_INVALID_ARG, "null argument");
+  if (n_resp == 0) return AV_OK;
+  RespTable rt;
+  AV_TRY(resp_table(e, n_resp, nodes, offsets, hashes, errs, status_out, rt));
+  const int64_t n = rt.n;
+  if (n == 0) {
+    e->facts.dropin_votes(rt.max_node_votes, false);
+    return AV_OK;
   }
-  AV_HIP(hipMemcpyAsync(hstat, dstat, (size_t)m, hipMemcpyDeviceToHost, e->stream));
-  AV_HIP(hipStreamSynchronize(e->stream));
-  parallel_chunks(n, 1 << 20, [&](int, int64_t a, int64_t b) {
-    for (int64_t i = a; i < b; ++i) status_out[i] = hstat[i];
+  AV_TRY(catalog_sync(e));
+  // ---- pinned: hashes (8 B each), errs, the Response table, then the status bytes
+  const uint32_t m = (uint32_t)n;
+  const size_t tab_words = resp_table_words(n_resp, rt);
+  AV_HIP(e->dropin_host.reserve((size_t)m * 13 + tab_words * 4 + 64, avmem::Slack::kMiB, hipHostMallocDefault));
+  auto* hhash = static_cast<int64_t*>(e->dropin_host.get());
+  auto* herr = reinterpret_cast<uint32_t*>(hhash + m);
+  auto* hoff = herr + m;
+  auto* hstat = reinterpret_cast<int8_t*>(hoff + tab_words);
+  fill_resp_table(e, n_resp, nodes, offsets, rt, hoff);
+  std::vector<uint8_t> neutral_t(64, 0);
+  parallel_chunks(n, 1 << 18, [&](int t, int64_t a, int64_t b) {
+    std::memcpy(hhash + a, hashes + a, (size_t)(b - a) * 8);
+    bool neutral = false;
+    for (int64_t v = a; v < b; ++v) {
+      const uint32_t err = errs[v];
+      herr[v] = err;
+      neutral |= (int32_t)err < 0;
+    }
+    neutral_t[t] = neutral;
   });
-  return AV_OK;
+  bool neutral = false;
+  for (int t = 0; t < 64; ++t) neutral |= neutral_t[t] != 0;
+  e->facts.dropin_votes(rt.max_node_votes, neutral);
+  // ---- device: hashes | errs | off | node | order | grp_off | packed | flag, pad | status bytes
+  const size_t in_words = 3 * (size_t)m + tab_words;
+  const size_t head_words = in_words + (size_t)m + 2 + ((size_t)m + 3) / 4;
+  void* buf = nullptr;
+  AV_TRY(engine_scratch(e, head_words * 4 + 64, &buf));
+  auto* dhash = static_cast<int64_t*>(buf);  // the allocation's start: 16-byte aligned
+  auto* derr = reinterpret_cast<uint32_t*>(dhash + m);
+  uint32_t* doff = derr + m;
+  uint32_t* dpack = doff + tab_words;
+  dpack += (in_words & 1u);  // 8-byte aligned (the kernel stores two packed votes at once)
+  uint32_t* dflag = dpack + m;
+  auto* dstat = reinterpret_cast<int8_t*>(dflag + 1);
+  AV_HIP(hipMemcpyAsync(dhash, hhash, in_words * 4, hipMemcpyHostToDevice, e->stream));
+  AV_HIP(hipMemsetAsync(dflag, 0, 4, e->stream));
+  AV_HIP(hipMemsetAsync(dstat, 0xFF, (size_t)m, e->stream));
+  AV_TRY(catalog_pack(e, dhash, derr, doff, (uint32_t)n_resp, m, dpack, dflag));
+  uint32_t unordered = 1;
+  AV_HIP(hipMemcpyAsync(&unordered, dflag, 4, hipMemcpyDeviceToHost, e->stream));
+  AV_HIP(hipStreamSynchronize(e->stream));
+  const bool fast = !unordered && e->dropin_fast;
+  uint32_t* grp = nullptr;
+  if (!fast) {
+    // the engine's scratch holds the batch: the grouping scratch is a buffer of its own, kept
+    AV_HIP(e->cat_group.reserve(group_words(m) + 128 + (size_t)avk::group_votes_scratch_words(m) * 2,
+                                avmem::Slack::kEighth));
+    grp = e->cat_group;
+  }
+  return apply_packed_votes(e, rt, n_resp, dpack, doff, dstat, fast, grp, hstat, status_out);
 }
 
 int av_read_records(av_engine* e, int64_t n0, int64_t n1, int64_t t0, int64_t t1, uint32_t* out) {

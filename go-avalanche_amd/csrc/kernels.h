@@ -10,6 +10,8 @@
 
 #include <type_traits>
 
+#include "catalog.h"
+
 namespace avk {
 
 // ---------------------------------------------------------------------------
@@ -508,6 +510,29 @@ hipError_t launch_group_votes(uint64_t* scratch, const uint32_t* keys, const uin
                               uint32_t n, int key_bits, uint32_t* keys_s, uint32_t* perm_s, uint32_t* keys_t,
                               uint32_t* perm_t, uint32_t* lanes, uint32_t* offs, uint32_t* n_runs, uint32_t* entries,
                               hipStream_t s);
+
+// ---- catalog.hip: the Hash catalog's device lookup
+// av_register_votes_hashed's lookup-and-pack (and av_catalog_find_device's parity dump): vote v's
+// hash is probed in the table image tab (catalog.h Entry, mask + 1 entries; slots local to the
+// engine's target range) and packed[v] = dropin_word(slot, catalogued, errs[v]) (errs null: err 0).
+// With n_resp > 0 the votes are the Responses resp_off[0 .. n_resp] (resp_off[0] = 0, resp_off[n_resp]
+// = n) and *unordered (zeroed by the caller) is set unless every Response can take the fast apply
+// path (launch_dropin_resp): its catalogued slots strictly ascending, and no uncatalogued vote
+// between two votes of one 32-slot block. hashes 16-byte aligned, packed 8-byte aligned.
+// entries of a table image that is staged into LDS: 32 KiB, which leaves a CU room for four
+// workgroups of the kernel (160 KiB per CU)
+constexpr uint32_t kCatLdsEntries = 2048;
+struct CatalogPackParams {
+  const avcat::Entry* tab;
+  const int64_t* hashes;
+  const uint32_t* errs;
+  const uint32_t* resp_off;
+  uint32_t* packed;
+  uint32_t* unordered;
+  uint32_t mask, n, n_resp;
+};
+// blocks: workgroups (0 = by size, at most 2048); lds: probe a staged copy (mask < kCatLdsEntries)
+hipError_t launch_catalog_pack(const CatalogPackParams& p, uint32_t blocks, bool lds, hipStream_t s);
 
 // ---- peer_ops.hip: the exchange of node-sharded engines
 // Device pointers of every rank's copy of a buffer, passed by value (kernel arguments: static

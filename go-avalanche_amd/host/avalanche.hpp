@@ -20,7 +20,6 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "avhip.h"
@@ -136,11 +135,24 @@ class Engine {
 
   av_engine* handle() const { return h_; }
   const EngineOptions& options() const { return opt_; }
-  // slot of a hash, or -1; Intern assigns a slot on first use (-1 if full)
+  // slot of a hash, or -1; Intern assigns a slot on first use (-1 if no slot is free). Both go
+  // through the engine's own catalog (av_catalog_find / av_catalog_intern), the one the device's
+  // hashed vote lookup reads: a new hash takes the lowest free slot.
   int64_t Find(Hash h) const;
   int64_t Intern(const Target& t);
   Hash HashOf(int64_t slot) const { return hashes_[slot]; }
   const std::string& TypeOf(int64_t slot) const { return types_[slot]; }
+  // The end of a target's life (the reference deletes the map entry on finalization, per Processor:
+  // processor.go:114-116): once no Processor of the engine holds a record of it, its hash leaves
+  // the catalog and its slot is free for the next new hash (av_catalog_retire). Pending
+  // StatusUpdates are fetched first (FetchUpdates / Rounds). False: not catalogued, or some
+  // Processor still holds a record.
+  bool Retire(const Target& t);
+  // RegisterVotes of many Processors in one call (av_register_votes_hashed: the hashes are looked up
+  // on the device): Processor nodes[i] registers responses[i]; a node may appear several times, its
+  // Responses apply in call order. updates[i] = the StatusUpdates RegisterVotes(responses[i]) appends.
+  void RegisterVotesBatch(const std::vector<NodeID>& nodes, const std::vector<Response>& responses,
+                          std::vector<std::vector<StatusUpdate>>* updates);
   // Push Target::IsValid() of every catalogued target whose value changed
   // (isWorthyPolling is evaluated dynamically: processor.go:185-187).
   void SyncValidity();
@@ -158,13 +170,14 @@ class Engine {
   // computes while round r's compact stream is copied (av_fetch_compact_async / _wait) and decoded.
   void Rounds(int32_t rounds, const Deliver& deliver);
   // Walk a compact StatusUpdate stream (include/avhip.h av_compact_header) in place: Hash through
-  // the catalog (a slot never interned is its own Hash).
+  // the catalog (a slot that holds no hash is its own Hash).
   void DecodeCompact(const void* stream, int64_t bytes, const Deliver& deliver) const;
 
  private:
   EngineOptions opt_;
   av_engine* h_ = nullptr;
-  std::unordered_map<Hash, int64_t> slot_of_;
+  // by slot (n_targets each): what the catalog holds there, and the Target object that answers
+  // IsValid() (nullptr: the slot holds no hash)
   std::vector<Hash> hashes_;
   std::vector<std::string> types_;
   std::vector<const Target*> targets_;

@@ -33,6 +33,12 @@ Engine::Engine(const EngineOptions& opt) : opt_(opt) {
   c.byz_threshold = opt.byz_threshold;
   c.device = opt.device;
   check(av_create(&c, &h_));
+  const size_t m = (size_t)opt.n_targets;
+  hashes_.resize(m);
+  for (size_t s = 0; s < m; ++s) hashes_[s] = (Hash)s;
+  types_.resize(m);
+  targets_.assign(m, nullptr);
+  valid_.assign(m, 1);  // engine slots start valid
 }
 
 Engine::~Engine() {
@@ -40,29 +46,60 @@ Engine::~Engine() {
 }
 
 int64_t Engine::Find(Hash h) const {
-  auto it = slot_of_.find(h);
-  return it == slot_of_.end() ? -1 : it->second;
+  int64_t s = -1;
+  check(av_catalog_find(h_, &h, 1, &s));
+  return s;
 }
 
 int64_t Engine::Intern(const Target& t) {
   const Hash h = t.GetHash();
-  int64_t s = Find(h);
-  if (s >= 0) {
-    targets_[s] = &t;  // the latest Target object answers IsValid()
-    return s;
+  int64_t s = -1;
+  check(av_catalog_intern(h_, &h, 1, &s));
+  if (s < 0) return -1;
+  if (!targets_[(size_t)s] || hashes_[(size_t)s] != h) {  // a new tenant of the slot
+    hashes_[(size_t)s] = h;
+    types_[(size_t)s] = t.Type();
+    valid_[(size_t)s] = 1;  // the engine made the slot valid for it
   }
-  if ((int64_t)hashes_.size() >= opt_.n_targets) return -1;
-  s = (int64_t)hashes_.size();
-  slot_of_[h] = s;
-  hashes_.push_back(h);
-  types_.push_back(t.Type());
-  targets_.push_back(&t);
-  valid_.push_back(1);  // engine slots start valid
+  targets_[(size_t)s] = &t;  // the latest Target object answers IsValid()
   return s;
+}
+
+bool Engine::Retire(const Target& t) {
+  const Hash h = t.GetHash();
+  const int64_t s = Find(h);
+  if (s < 0) return false;
+  uint8_t gone = 0;
+  check(av_catalog_retire(h_, &h, 1, 1, &gone));
+  if (gone) targets_[(size_t)s] = nullptr;
+  return gone != 0;
+}
+
+void Engine::RegisterVotesBatch(const std::vector<NodeID>& nodes, const std::vector<Response>& responses,
+                                std::vector<std::vector<StatusUpdate>>* updates) {
+  if (nodes.size() != responses.size()) throw Error(AV_ERR_INVALID_ARG, "one node per Response");
+  SyncValidity();
+  std::vector<int64_t> offsets(responses.size() + 1, 0), hashes;
+  std::vector<uint32_t> errs;
+  for (size_t i = 0; i < responses.size(); ++i) {
+    for (const Vote& v : responses[i].GetVotes()) {
+      hashes.push_back(v.GetHash());
+      errs.push_back(v.GetError());
+    }
+    offsets[i + 1] = (int64_t)hashes.size();
+  }
+  std::vector<int32_t> status(hashes.size(), -1);
+  check(av_register_votes_hashed(h_, (int64_t)responses.size(), nodes.data(), offsets.data(), hashes.data(),
+                                 errs.data(), status.data()));
+  updates->assign(responses.size(), {});
+  for (size_t i = 0; i < responses.size(); ++i)
+    for (int64_t v = offsets[i]; v < offsets[i + 1]; ++v)
+      if (status[(size_t)v] >= 0) (*updates)[i].push_back({hashes[(size_t)v], static_cast<Status>(status[(size_t)v])});
 }
 
 void Engine::SyncValidity() {
   for (size_t s = 0; s < targets_.size(); ++s) {
+    if (!targets_[s]) continue;
     const int8_t v = targets_[s]->IsValid() ? 1 : 0;
     if (v != valid_[s]) {
       check(av_set_valid(h_, (int64_t)s, v));
@@ -146,7 +183,7 @@ void Engine::DecodeCompact(const void* stream, int64_t bytes, const Deliver& del
         uint32_t code = 0;
         std::memcpy(&code, g + at + 8 + (size_t)i * cw, cw);  // little-endian 2- or 4-byte code
         const int64_t slot = h.target_base + (int64_t)((code >> 2) & tmask);
-        ups[i].hash = slot < (int64_t)hashes_.size() ? hashes_[(size_t)slot] : (Hash)slot;
+        ups[i].hash = slot >= 0 && slot < (int64_t)hashes_.size() ? hashes_[(size_t)slot] : (Hash)slot;
         ups[i].status = (Status)(code & 3u);
       }
       deliver(round, (NodeID)node, ups);

@@ -26,6 +26,7 @@ AV_OK = 0
 AV_ERR_INVALID_ARG = -1
 AV_ERR_NOT_FOUND = -4
 AV_ERR_OVERFLOW = -5
+AV_ERR_UNSUPPORTED = -6
 AV_ERR_PEER = -8
 
 STATUS_INVALID, STATUS_REJECTED, STATUS_ACCEPTED, STATUS_FINALIZED = 0, 1, 2, 3
@@ -100,6 +101,8 @@ EXPORTED = [
     "av_pushed_words", "av_log_entries", "av_resize_log", "av_fetch_compact", "av_fetch_compact_async",
     "av_fetch_compact_wait", "av_compact_expand", "av_update_round_shift", "av_net_quiet_rounds",
     "av_add_targets_batch", "av_admit_targets",
+    "av_catalog_intern", "av_catalog_find", "av_catalog_find_device", "av_catalog_hashes", "av_catalog_retire",
+    "av_register_votes_hashed",
 ]
 
 _lib = None
@@ -181,6 +184,12 @@ def lib():
         "av_fetch_compact_wait": (i32, [_vp, i64, P(_vp), P(i64)]),
         "av_compact_expand": (i32, [_vp, i64, _vp, i64, P(i64)]),
         "av_update_round_shift": (i32, [_vp, P(i32)]),
+        "av_catalog_intern": (i32, [_vp, _vp, i64, _vp]),
+        "av_catalog_find": (i32, [_vp, _vp, i64, _vp]),
+        "av_catalog_find_device": (i32, [_vp, _vp, i64, _vp]),
+        "av_catalog_hashes": (i32, [_vp, _vp, _vp]),
+        "av_catalog_retire": (i32, [_vp, _vp, i64, i32, _vp]),
+        "av_register_votes_hashed": (i32, [_vp, i64, _vp, _vp, _vp, _vp, _vp]),
     }
     for name, (res, args) in sig.items():
         if name == "av_net_quiet_rounds" and os.environ.get("AVHIP_LIB") and not hasattr(L, name):
@@ -403,6 +412,59 @@ class Engine:
         st = np.zeros(max(1, t.size), np.int32)
         _check(lib().av_register_votes_batch(self._h, nd.size, _ptr(nd), _ptr(of), _ptr(t), _ptr(e), _ptr(st)))
         return st[: t.size]
+
+    # ---- the Hash catalog: the caller's 64-bit hashes <-> this engine's target slots ----
+    def _catalog_lookup(self, fn, hashes):
+        h = np.ascontiguousarray(hashes, np.int64)
+        out = np.zeros(max(1, h.size), np.int64)
+        _check(fn(self._h, _ptr(h), h.size, _ptr(out)))
+        return out[: h.size]
+
+    def catalog_intern(self, hashes):
+        """Slots of the hashes, in call order (av_catalog_intern): a catalogued hash keeps its slot,
+        a new one takes the lowest free slot of the target range, -1 when none is free."""
+        return self._catalog_lookup(lib().av_catalog_intern, hashes)
+
+    def catalog_find(self, hashes):
+        """Slots of the hashes from the host catalog, -1 = not catalogued (av_catalog_find)."""
+        return self._catalog_lookup(lib().av_catalog_find, hashes)
+
+    def catalog_find_device(self, hashes):
+        """The same answers from the device table, by the hashed vote call's lookup kernel."""
+        return self._catalog_lookup(lib().av_catalog_find_device, hashes)
+
+    def catalog_hashes(self):
+        """(hashes int64[local targets], used bool[local targets]): the catalog by slot."""
+        tn = self.target_range[1] - self.target_range[0]
+        h, u = np.zeros(tn, np.int64), np.zeros(tn, np.uint8)
+        _check(lib().av_catalog_hashes(self._h, _ptr(h), _ptr(u)))
+        return h, u.astype(bool)
+
+    def catalog_retire(self, hashes, commit=True):
+        """bool[n]: the hashes that are catalogued and whose slot no local node holds a record of
+        (av_catalog_retire); commit: remove them and free their slots (fetch the pending
+        StatusUpdates first)."""
+        h = np.ascontiguousarray(hashes, np.int64)
+        out = np.zeros(max(1, h.size), np.uint8)
+        _check(lib().av_catalog_retire(self._h, _ptr(h), h.size, int(bool(commit)), _ptr(out)))
+        return out[: h.size].astype(bool)
+
+    def register_votes_hashed(self, nodes, offsets, hashes, errs):
+        """register_votes_batch with the caller's hashes in place of slots (av_register_votes_hashed):
+        the device looks them up; a hash that is not catalogued is skipped (status -1)."""
+        nd = np.ascontiguousarray(nodes, np.int64)
+        of = np.ascontiguousarray(offsets, np.int64)
+        h = np.ascontiguousarray(hashes, np.int64)
+        e = np.ascontiguousarray(errs, np.uint32)
+        if of.size != nd.size + 1:
+            raise ValueError(f"offsets has {of.size} entries, expected len(nodes) + 1 = {nd.size + 1}")
+        if of[0] != 0 or np.any(np.diff(of) < 0):
+            raise ValueError("offsets must start at 0 and be non-decreasing")
+        if not (h.size == e.size == of[-1]):
+            raise ValueError(f"hashes ({h.size}) and errs ({e.size}) must both have offsets[-1] = {of[-1]} entries")
+        st = np.zeros(max(1, h.size), np.int32)
+        _check(lib().av_register_votes_hashed(self._h, nd.size, _ptr(nd), _ptr(of), _ptr(h), _ptr(e), _ptr(st)))
+        return st[: h.size]
 
     def is_accepted(self, node, target):
         out = C.c_int32(0)

@@ -194,6 +194,59 @@ int av_register_votes(av_engine* e, int64_t node, const int64_t* targets, const 
 int av_register_votes_batch(av_engine* e, int64_t n_resp, const int64_t* nodes, const int64_t* offsets,
                             const int64_t* targets, const uint32_t* errs, int32_t* status_out);
 int av_is_accepted(av_engine* e, int64_t node, int64_t target, int32_t* out);
+
+/* ---- the Hash catalog (avalanche.go:71: `type Hash int`, any 64-bit value) ----
+ * Every engine owns a catalog that maps the caller's hashes to the slots of its
+ * own target range [target_begin, target_end), the place of the reference's
+ * map keys (the Processor's record map, processor.go:17). Opt-in: an
+ * engine whose catalog is empty behaves as before, and every call that takes
+ * slots keeps working on any slot, catalogued or not. The host side is
+ * authoritative; the device holds a copy of its table that the hashed vote call
+ * probes. The slot rule is deterministic: hashes are interned in call order, a
+ * new hash takes the lowest free slot of the range, a catalogued one keeps its
+ * slot. Every int64 is a legal hash. */
+/* The map insert of AddTargetToReconcile (processor.go:50-56), without the
+ * record: slots[i] = the slot of hashes[i], its own if it
+ * is catalogued (a duplicate inside the call included), else the lowest free
+ * slot, else -1 with nothing changed (no free slot). A new hash whose slot is
+ * invalid (av_set_valid of its previous tenant) makes the slot valid again.
+ * The caller then adds records with the slot calls (av_add_targets*,
+ * av_admit_targets). */
+int av_catalog_intern(av_engine* e, const int64_t* hashes, int64_t n, int64_t* slots);
+/* The map lookup of RegisterVotes (processor.go:95) on the host:
+ * slots[i] = the slot of hashes[i], or -1 if it is not catalogued. */
+int av_catalog_find(av_engine* e, const int64_t* hashes, int64_t n, int64_t* slots);
+/* The same answers from the device copy of the table, by the lookup kernel of
+ * av_register_votes_hashed (a parity dump, as av_sample_peers is for the peer
+ * draw; processor.go:95). */
+int av_catalog_find_device(av_engine* e, const int64_t* hashes, int64_t n, int64_t* slots);
+/* The catalog by slot, [local targets] each: used[s] = 1 iff slot target_begin
+ * + s holds a hash, hashes[s] = that hash (0 where unused): what turns the
+ * target field of a StatusUpdate (avalanche.go:59-62) back into its Hash. */
+int av_catalog_hashes(av_engine* e, int64_t* hashes, uint8_t* used);
+/* The end of a hash's life: the reference deletes the map entry on
+ * finalization (processor.go:114-116), per Processor; a slot serves every
+ * node, so it is free again once no node holds a record of it. retirable[i] =
+ * 1 iff hashes[i] is catalogued and no local node holds a record of its slot
+ * (a record of an invalid target is still a record), read from the device
+ * stream-ordered after the rounds enqueued, the deferred state left in place
+ * (as av_census). commit = 0 changes nothing. commit != 0 removes the hashes
+ * reported 1 and frees their slots (a repeated hash reports the same value at
+ * each position and is freed once); with StatusUpdates pending
+ * (av_updates_count > 0) it returns AV_ERR_UNSUPPORTED and changes nothing:
+ * update words carry slots, so the caller fetches first. Node shards: ask every
+ * shard with commit = 0, combine, then commit the hashes every shard reported
+ * (INTEGRATION.md). */
+int av_catalog_retire(av_engine* e, const int64_t* hashes, int64_t n, int32_t commit, uint8_t* retirable);
+/* av_register_votes_batch with the caller's hashes in place of slots
+ * (processor.go:61-122 per Response; the lookup of :95 on the device). A hash
+ * that is not catalogued is skipped as the reference skips an unknown hash
+ * (processor.go:95-99), status_out -1. Everything else is the slot call on the
+ * translated slots: order inside a node, duplicates, neutral votes, invalid
+ * targets, records finalizing inside the batch, the limits, and
+ * AV_ERR_UNSUPPORTED on a peer-push engine. */
+int av_register_votes_hashed(av_engine* e, int64_t n_resp, const int64_t* nodes, const int64_t* offsets,
+                             const int64_t* hashes, const uint32_t* errs, int32_t* status_out);
 /* AV_ERR_NOT_FOUND where the reference panics "VoteRecord not found". */
 int av_get_confidence(av_engine* e, int64_t node, int64_t target, uint16_t* out);
 /* Live valid targets in ascending index, truncated to 4096. */
@@ -470,7 +523,10 @@ int av_sample_peers(av_engine* e, int64_t round, int64_t n0, int64_t n1, int32_t
  * "admit_map" (0: av_admit_targets' thread mapping by the touched blocks;
  * 1: a wave per 64 nodes of one block; 2: lane-major; exact),
  * "push_store" (1: plain peer stores; 0: system scope; 2: none, results
- * invalid), "census_blocks" (0: av_census's grid by size).
+ * invalid), "census_blocks" (0: av_census's grid by size),
+ * "catalog_blocks" (0: the hash lookup kernel's grid by size, at most 2048
+ * workgroups), "catalog_lds" (1: a hash table of <= 2048 entries is staged into
+ * LDS; 0: probed in global memory at any size; exact).
  * StatusUpdate delivery: "enc_buckets" (2^26: (round, node) buckets per
  * encoder pass; a log spanning more takes several passes), "copy_blocks" (0:
  * the compact stream's copy to host memory by the runtime's copy; n: by an
