@@ -303,7 +303,7 @@ int fill_row_params(av_engine* e, avk::RoundPlan& plan, int nb, avk::RoundParams
     plan.uni_rows = plan.uni_rows && e->ref_node >= 0;
   }
   if (plan.ref_rows && e->round - e->rflag_clear_round >= 120) {
-    // flag bytes carry a 7-bit snapshot tag (round_sweep.hip ref_tag): every buffer's flags are
+    // flag bytes carry a 7-bit snapshot tag (sweep_publish.h ref_tag): every buffer's flags are
     // cleared before 128 rounds have passed since the last clear, whatever kind of round ran in
     // between (replay, capped, non-refr), so no byte outlives its tag's period
     for (int b = 0; b < 3; ++b)

@@ -173,12 +173,12 @@ struct av_engine {
   // (kModeWarm; default); 0 = the prefetching kModeWarmPipe (A/B)
   bool sweep_nopipe = true;
   // option "wave_runs": a walking grid gives each wave a run of consecutive
-  // tiles whose peers one Philox pass draws (round_sweep.hip WaveDraw)
+  // tiles whose peers one Philox pass draws (sweep_tile.h WaveDraw)
   bool wave_runs = true;
   // option "settled_fast": settled warm tiles skip the round step's bookkeeping
   bool settled_fast = true;
   // option "settled_lean": with BL dividing 64, a wave tests its run's settled candidates in one
-  // lean loop first (round_sweep.hip settled_run)
+  // lean loop first (sweep_settled.h settled_run)
   bool settled_lean = true;
   // option "tiles_per_wave" (default grid, default_sweep_blocks); 0 = by size: up to 16, at most BL, with
   // >= 15000 waves (C4: 500k tiles, 16 per wave; C3's 98k tiles: 4 — 8 per wave leaves two generations

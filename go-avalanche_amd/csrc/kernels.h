@@ -79,7 +79,7 @@ constexpr uint32_t kVStale = 1u, kVUniform = 2u, kVMask = 3u, kCAll = 4u;
 // vstale bit 3, outside kVMask and only ever set together with kVStale (RoundParams::calm): V is
 // stale, and every polled record of the tile has at most one of V0..V6 differing from its accepted
 // bit as stored. Whoever masks with kVMask sees a stale tile; the settled tests of the next klazy
-// round (round_sweep.hip) take the tile as a candidate with no regather.
+// round (sweep_settled.h) take the tile as a candidate with no regather.
 constexpr uint32_t kVCalm = 8u;
 
 // Division by the (runtime) block count BL without a hardware divide:
@@ -238,7 +238,7 @@ struct RoundParams {
   uint8_t* stale;       // nullptr: unmasked pushes (every changed word to every peer)
   uint32_t segs;        // 32-word segments per row: ceil(BL / 32)
   uint32_t peer_all;    // (1 << push_n) - 1
-  // the pushes queued in LDS and stored after a wave's last tile (round_sweep.hip flush_pushes): the
+  // the pushes queued in LDS and stored after a wave's last tile (sweep_publish.h flush_pushes): the
   // sweep's waves each take at most kPushQ tiles and push_n <= 8 (a byte per lane and tile)
   uint32_t push_q;
   uint32_t push_defer;  // engine option "push_defer" (default 1): the sweep may queue its pushes (push_q)
@@ -282,7 +282,7 @@ struct RoundParams {
   // can only read as a mismatch (tags are unique per round), never hide one.
   uint32_t* uni_out;
   const uint32_t* uni_in;
-  const uint32_t* uni_prev;  // pref_prev + uni_off (nullptr: its slots not maintained); round_sweep.hip kUniPrev
+  const uint32_t* uni_prev;  // pref_prev + uni_off (nullptr: its slots not maintained); sweep_tile.h kUniPrev
   uint32_t uni_world, uni_rank, uni_off;
   uint32_t uni_merge;  // a round with a uniform input: every uni_merge-th wave takes uni_merge runs (1: off)
   uint32_t uni_post;   // peer-push rounds: the rank's slot reaches the peers after the round (launch_peer_barrier)
@@ -295,9 +295,9 @@ struct RoundParams {
   uint32_t tn;
   uint32_t hivirt;  // k = 8 sweep rounds may leave the K4..K7 group unstored (kHiVirt)
   uint32_t tpw;     // kModeWarm, k = 8: run length of consecutive tiles per wave with one shared peer draw (0 = grid stride)
-  uint32_t settled_fast;  // kModeWarm, k = 8: settled tiles skip process_tile (round_sweep.hip settled_fast)
+  uint32_t settled_fast;  // kModeWarm, k = 8: settled tiles skip process_tile (sweep_settled.h settled_tile)
   // kModeWarm, k = 8, BL dividing 64 (a lane's block is lane % BL): the settled candidates of a wave's
-  // run are tested first in one lean loop (round_sweep.hip settled_run); bl_log2 = log2(BL)
+  // run are tested first in one lean loop (sweep_settled.h settled_run); bl_log2 = log2(BL)
   uint32_t lean;
   uint32_t bl_log2;
   uint32_t nopipe;  // tuning: a grid smaller than the tile count runs kModeWarm (no next-tile prefetch)
@@ -313,10 +313,10 @@ struct RoundParams {
   const uint32_t* nopoll;
   uint32_t dense_min;  // a lane with >= dense_min updates logs one dense record (default dense_min(k))
   uint32_t uni_votes;  // k = 8 warm sweep, uniform input (uni_in): general-path tiles take the reference word
-                       // as their 8 votes instead of gathering them (option "uni_votes"; round_sweep.hip load_tile)
+                       // as their 8 votes instead of gathering them (option "uni_votes"; sweep_tile.h load_tile)
   uint32_t quiet_tiles;  // k = 8 warm sweep, single-engine build (option "quiet_tiles", default 1): a settled tile
                          // with two deferred rounds behind it and uniform input snapshots takes its +8 step with
-                         // no A-plane read and no republished row (round_sweep.hip "Quiescent tiles")
+                         // no A-plane read and no republished row (sweep_settled.h "Quiescent tiles")
   // Calm tiles (k = 8 warm sweep, klazy rounds with stale votes, not the uniform-only form; option
   // "calm_tiles", default 1; round_plan.h RoundPlan::calm). A general tile that leaves V
   // unstored and is not settled flags itself kVCalm when, on every polled record, at most one of this
@@ -327,7 +327,7 @@ struct RoundParams {
   // 0: the flag is neither set nor taken.
   uint32_t calm;
   // Network-quiet rounds (k = 8 warm sweep, single-engine build, klazy rounds with quiet_tiles; option
-  // "net_quiet", default 1; round_sweep.hip "Network-quiet rounds"). Two device words, used by round
+  // "net_quiet", default 1; sweep_settled.h "Network-quiet rounds"). Two device words, used by round
   // parity. nq_out: this round's word; a wave that owns tiles and whose run is not quiescent throughout
   // stores p.round + 1 into it, a fully quiescent wave stores nothing. nq_in: the word the round before
   // wrote (nullptr: not maintained, or something wrote records, tile words, rows or options since:
@@ -411,7 +411,8 @@ hipError_t launch_round(const RoundParams& p, int k, bool replay, bool capped, h
 // records queried this round that their responder did not hold.
 hipError_t launch_readd(const RoundParams& p, hipStream_t s);
 
-// ---- round_sweep.hip: the persistent streaming round, uncapped, k <= 8
+// ---- round_sweep.hip: the persistent streaming round, uncapped, k <= 8 (k_round_sweep itself and its
+// launcher templates: sweep_kernel.h; this unit compiles k = 8 and forwards every other k)
 // k_round_sweep: `blocks` workgroups of 256 threads sweep the tiles; 0 = one wave per tile.
 // mode: the round plan's (round_plan.h plan_round)
 // ref_written (may be null): whether the launch wrote p.rflag_out (only the walking warm mode does)
@@ -425,6 +426,13 @@ hipError_t round_sweep_occupancy(int k, bool replay, int* blocks_per_cu, int* cu
 // do_v: the V planes of stale tiles (p.vstale, p.pref_prev, p.round = the round after the one that
 // left them stale); do_k: the pending +8 steps of deferred count planes (p.kpend), then cleared.
 hipError_t launch_materialize(const RoundParams& p, bool do_v, bool do_k, hipStream_t s);
+
+// ---- round_sweep_lowk.hip: the same kernel at k = 1..7 (hipErrorInvalidValue for any other k);
+// called by the two functions above only (hidden: the library's dynamic symbols stay what they were)
+__attribute__((visibility("hidden"))) hipError_t launch_round_sweep_lowk(const RoundParams& p, int k, SweepMode mode,
+                                                                         uint32_t blocks, hipStream_t s,
+                                                                         bool* ref_written);
+__attribute__((visibility("hidden"))) hipError_t round_sweep_occupancy_lowk(int k, bool replay, int* blocks_per_cu);
 
 // ---- round_node.hip: the capped round, k <= 8
 // k_replay_node: p.fuse_rounds replay rounds of every node in one launch (capped engines, k <= 8);

@@ -15,7 +15,7 @@ enum class RoundKernel : int {
   FirstGen,  // k_round_fast / k_round_capped (any k; responder variants, non-polling nodes, A/B)
 };
 
-// The sweep kernel's build, as far as the records decide it. The launcher (round_sweep.hip
+// The sweep kernel's build, as far as the records decide it. The launcher (sweep_kernel.h
 // launch_sweep_k) adds what depends on the grid alone: Warm runs as the walking kModeWarm or, on a
 // resident grid smaller than the tile count, as kModeWarmPipe.
 enum class SweepMode : int { Replay, Ablate, Fresh, Warm, Check };
@@ -110,7 +110,7 @@ struct RecordFacts {
   // the network-quiet word of the last round (kernels.h nq_in) says whether some run of that round was
   // not quiescent, and nothing has written a record plane, a tile word, a validity word, a snapshot
   // row or an option since: set by after_round of a klazy sweep round that maintained the word,
-  // cleared by everything else listed above k_round_sweep ("Network-quiet rounds")
+  // cleared by everything else listed in sweep_settled.h ("Network-quiet rounds")
   bool nq_ok = false;
 
   // Anything but a reference-row sweep round that writes a snapshot buffer

@@ -1,4 +1,4 @@
-"""Calm tiles (round_sweep.hip, option calm_tiles, default on): a general tile of a klazy
+"""Calm tiles (sweep_tile.h process_tile, sweep_settled.h; option calm_tiles, default on): a general tile of a klazy
 round that leaves its vote planes unstored and is not settled flags itself kVCalm when every
 polled record has at most one of the round's slots 1..7 (next round's V6..V0) differing from
 its final accepted bit. The next klazy round takes such a tile as a settled candidate: if its 8

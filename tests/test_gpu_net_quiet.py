@@ -1,4 +1,4 @@
-"""Network-quiet rounds (round_sweep.hip, option net_quiet, default on): when every
+"""Network-quiet rounds (sweep_settled.h, option net_quiet, default on): when every
 run of the network was quiescent in round r - 1 and nothing was written since, round
 r adds the deferred count step to the tile words alone: a leader wave takes
 net_quiet_group runs, the others end at once. Bytes, applied votes, records,

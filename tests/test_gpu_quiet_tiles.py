@@ -1,4 +1,4 @@
-"""Quiescent tiles (round_sweep.hip, option quiet_tiles, default on): a settled
+"""Quiescent tiles (sweep_settled.h, option quiet_tiles, default on): a settled
 tile that deferred its count step in the two rounds before this one, in a round
 whose input snapshot and the one before it are both uniform, and whose run holds
 no Byzantine node, takes one more deferred +8 step with no A-plane read and no

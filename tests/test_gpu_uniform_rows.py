@@ -3,7 +3,7 @@ publishes when some published word differs from the reference node's word of
 the round's input snapshot; when the input snapshot carries no tag, every row
 of it IS the reference row of the snapshot before, so each gathered vote is
 that row's word whoever the peers are, and settled-candidate tiles are tested
-with no peer draw and no gather (round_sweep.hip settled_run_uni).
+with no peer draw and no gather (sweep_settled.h settled_run_uni).
 
 Checked against the oracle (every StatusUpdate, the records, the published
 rows) through convergence, the settled rounds and finalization, with API calls
@@ -137,7 +137,7 @@ def test_uni_merge_on_off_identical(tpw, merge, m):
 
 @pytest.mark.parametrize("m,byz", [(1000, 0), (125, 0), (1000, BYZ20)], ids=["bl32", "bl4", "bl32_byz"])
 def test_uni_votes_on_off_identical_and_taken(m, byz):
-    """Option uni_votes (round_sweep.hip load_tile): with a uniform input snapshot the tiles that
+    """Option uni_votes (sweep_tile.h load_tile): with a uniform input snapshot the tiles that
     are not settled candidates take the reference word as their 8 votes instead of gathering them.
     Same digests, records, published rows and finalizations as with it off, through convergence,
     the settled rounds and the finalization storm; with honest voters the converging rounds move
