@@ -235,7 +235,8 @@ namespace {
 
 avk::PlanShape plan_shape(const av_engine* e) {
   return {e->k,      e->BL,         e->N,               e->NL,       e->PS,
-          e->capped, e->peer_world, e->comm != nullptr, e->pub_mode, e->any_nopoll};
+          e->capped, e->peer_world, e->comm != nullptr, e->pub_mode, e->any_nopoll,
+          e->lossy(), e->loss_neutral};
 }
 avk::PlanKnobs plan_knobs(const av_engine* e) {
   return {e->kernel,   e->virtual_votes, e->vv_min_bl,     e->count_lazy,     e->k_hi_virtual,
@@ -387,6 +388,15 @@ int exchange_tail(av_engine* e, const avk::RoundParams& p, int nb, hipEvent_t ev
 int launch_one_round(av_engine* e, const uint32_t* replay) {
   AV_TRY(round_checks(e, 1));
   avk::RoundPlan plan = plan_for(e, replay != nullptr);
+  if (plan.unsupported && plan.lossy) {  // rule R5: no kernel runs these with lost Responses
+    AV_CHECK(!e->capped, AV_ERR_UNSUPPORTED,
+             "rounds with lost Responses or unresponsive nodes (av_set_loss, av_set_responding) need M <= 4096 "
+             "(uncapped)");
+    AV_CHECK(e->pub_mode != 2, AV_ERR_UNSUPPORTED,
+             "rounds with lost Responses or unresponsive nodes: not with the example responder (responder 2)");
+    AV_CHECK(e->peer_world <= 1, AV_ERR_UNSUPPORTED,
+             "rounds with lost Responses or unresponsive nodes: not on a peer-push engine");
+  }
   AV_CHECK(!plan.unsupported, AV_ERR_UNSUPPORTED,
            "the example responder and av_set_polling need M <= 4096 (uncapped)");
   AV_TRY(materialize(e, plan.wb_votes || plan.wb_cpreset, false));  // (two passes, votes first)
@@ -434,6 +444,15 @@ int launch_one_round(av_engine* e, const uint32_t* replay) {
     case avk::RoundKernel::FirstGen:
       AV_HIP(avk::launch_round(p, e->k, plan.replay, e->capped, e->stream));
       break;
+    case avk::RoundKernel::Lossy: {
+      avk::LossyParams lp{};
+      lp.r = p;
+      lp.responding = e->any_down ? e->responding.get() : nullptr;
+      lp.lost = e->lost;
+      lp.loss_threshold = e->loss_threshold;
+      AV_HIP(avk::launch_round_lossy(lp, e->k, plan.loss_neutral, e->stream));
+      break;
+    }
   }
   if (e->pub_mode == 2) {  // the responders' re-adds (main.go:175-177)
     AV_HIP(avk::launch_readd(p, e->stream));

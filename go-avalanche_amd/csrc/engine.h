@@ -283,6 +283,16 @@ struct av_engine {
   std::vector<uint32_t> nopoll_host;
   avmem::DevBuf<uint32_t> nopoll;    // [ceil(NL/32)]
   bool any_nopoll = false;
+  // lost Responses and unresponsive nodes (rule R5; av_set_loss, av_set_responding): sim rounds run
+  // k_round_lossy while lossy() holds. responding: bit n = node n of the whole network answers
+  // queries; allocated, like the counter, by the first call that needs it
+  uint32_t loss_threshold = 0;
+  bool loss_neutral = false;
+  std::vector<uint32_t> responding_host;
+  avmem::DevBuf<uint32_t> responding;           // [ceil(N/32)]
+  bool any_down = false;
+  avmem::DevBuf<unsigned long long> lost;       // [kLogShards] lost Responses (av_lost_responses)
+  bool lossy() const { return loss_threshold != 0 || any_down; }
   // per-local-node Processor.round (processor.go:15,40-42): a field only the
   // caller changes (avalanche_test.go:302); allocated on the first set
   std::vector<int64_t> proc_round;

@@ -661,6 +661,71 @@ int av_set_polling(av_engine* e, int64_t node, int32_t polls) {
   return AV_OK;
 }
 
+// Rule R5. A Response that does not arrive is a RegisterVotes call that returns before it reads a
+// vote (processor.go:66-76, AvalancheRequestTimeout avalanche.go:19-21): with that check disabled,
+// a call that never happens (AV_LOSS_SKIP); a neutral one shifts consider = 0 (vote.go:55-56).
+int av_set_loss(av_engine* e, uint32_t loss_threshold, int32_t mode) {
+  AV_ENTER(e);
+  AV_CHECK(mode == AV_LOSS_SKIP || mode == AV_LOSS_NEUTRAL, AV_ERR_INVALID_ARG, "bad loss mode");
+  AV_CHECK(loss_threshold == 0 || e->peer_world <= 1, AV_ERR_UNSUPPORTED, "av_set_loss on a peer-push engine");
+  if (loss_threshold && !e->lost) AV_HIP(e->lost.alloc_zeroed(avk::kLogShards, e->stream));
+  e->loss_threshold = loss_threshold;
+  e->loss_neutral = mode == AV_LOSS_NEUTRAL;
+  return AV_OK;
+}
+
+int av_set_responding(av_engine* e, const int64_t* nodes, int64_t n, int32_t responds) {
+  AV_ENTER(e);
+  AV_CHECK(n >= 0 && (nodes || n == 0), AV_ERR_INVALID_ARG, "null argument");
+  for (int64_t i = 0; i < n; ++i)
+    AV_CHECK(nodes[i] >= 0 && nodes[i] < e->N, AV_ERR_INVALID_ARG, "node %lld outside the network", (long long)nodes[i]);
+  AV_CHECK(responds || n == 0 || e->peer_world <= 1, AV_ERR_UNSUPPORTED,
+           "av_set_responding(0) on a peer-push engine");
+  if (n == 0 || (responds && !e->any_down)) return AV_OK;  // every node responds already
+  const size_t words = (size_t)((e->N + 31) / 32);
+  if (e->responding_host.empty()) {
+    e->responding_host.assign(words, ~0u);
+    AV_HIP(e->responding.alloc(words));
+  }
+  if (!e->lost) AV_HIP(e->lost.alloc_zeroed(avk::kLogShards, e->stream));
+  for (int64_t i = 0; i < n; ++i) {
+    uint32_t& w = e->responding_host[(size_t)(nodes[i] >> 5)];
+    const uint32_t bit = 1u << (nodes[i] & 31);
+    w = responds ? (w | bit) : (w & ~bit);
+  }
+  AV_HIP(hipMemcpyAsync(e->responding, e->responding_host.data(), words * 4, hipMemcpyHostToDevice, e->stream));
+  AV_HIP(hipStreamSynchronize(e->stream));
+  e->any_down = false;
+  for (int64_t node = 0; node < e->N && !e->any_down; node += 32) {
+    const uint32_t all = e->N - node >= 32 ? ~0u : (1u << (e->N - node)) - 1u;
+    e->any_down = (e->responding_host[(size_t)(node >> 5)] & all) != all;
+  }
+  return AV_OK;
+}
+
+// The device's own answer (a parity dump, as av_sample_peers is of R1's draw): 1 = the Response of
+// that slot is lost, by the draw or because its peer does not respond.
+int av_sample_lost(av_engine* e, int64_t round, int64_t n0, int64_t n1, uint8_t* out) {
+  AV_ENTER(e);
+  AV_CHECK(out && n0 >= 0 && n0 <= n1 && n1 <= e->N && round >= 0, AV_ERR_INVALID_ARG, "bad range");
+  const size_t n = (size_t)(n1 - n0) * e->k;
+  if (!n) return AV_OK;
+  avmem::DevBuf<uint8_t> s;
+  AV_HIP(s.alloc(n));
+  AV_HIP(avk::launch_sample_lost(e->cfg.seed, (uint32_t)e->N, (uint32_t)n0, (uint32_t)n1, (uint32_t)round, e->k,
+                                 e->cfg.peer_mode, e->loss_threshold, e->any_down ? e->responding.get() : nullptr, s,
+                                 e->stream));
+  AV_HIP(hipMemcpyAsync(out, s, n, hipMemcpyDeviceToHost, e->stream));
+  AV_HIP(hipStreamSynchronize(e->stream));
+  return AV_OK;
+}
+
+int av_lost_responses(av_engine* e, int64_t* out) {
+  AV_TRY(counter_query(e, out));
+  *out = 0;
+  return e->lost ? sum_shards(e, e->lost, out) : AV_OK;
+}
+
 int av_applied_votes(av_engine* e, int64_t* out) {
   AV_TRY(counter_query(e, out));
   return sum_shards(e, e->applied, out);

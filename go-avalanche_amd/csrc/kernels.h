@@ -411,6 +411,26 @@ hipError_t launch_round(const RoundParams& p, int k, bool replay, bool capped, h
 // records queried this round that their responder did not hold.
 hipError_t launch_readd(const RoundParams& p, hipStream_t s);
 
+// ---- round_lossy.hip: the round with lost Responses and unresponsive nodes (rule R5), uncapped, k <= 16
+// The Response of slot s of node n in round r is lost iff x[s & 3] < loss_threshold, x =
+// philox4x32-10({n, r, s >> 2, 6}, seed), or its peer (R1's draw) has its bit clear in `responding`.
+// RoundParams itself is left as it is (every other kernel takes it by value): the round's extra
+// arguments ride behind it.
+struct LossyParams {
+  RoundParams r;
+  const uint32_t* responding;  // [ceil(N/32)] bit n: node n answers queries (nullptr: every node does)
+  unsigned long long* lost;    // [kLogShards] lost Responses of polling local nodes, once per (node, slot)
+  uint32_t loss_threshold;
+};
+// neutral = false (AV_LOSS_SKIP): a lost slot registers nothing (the RegisterVotes call that never
+// happens, processor.go:66-76); true (AV_LOSS_NEUTRAL): it registers err = 0x80000000 for every
+// polled target (vote.go:55-56). Honours nopoll, valid, pub_mode 0 / 1, died_out, plane_nt.
+hipError_t launch_round_lossy(const LossyParams& p, int k, bool neutral, hipStream_t s);
+// The same answer for nodes [a, b) of `round`, [b - a][k] bytes, 1 = lost (av_sample_lost)
+hipError_t launch_sample_lost(uint64_t seed, uint32_t n_nodes, uint32_t a, uint32_t b, uint32_t round, int k,
+                              int mode, uint32_t loss_threshold, const uint32_t* responding, uint8_t* out,
+                              hipStream_t s);
+
 // ---- round_sweep.hip: the persistent streaming round, uncapped, k <= 8 (k_round_sweep itself and its
 // launcher templates: sweep_kernel.h; this unit compiles k = 8 and forwards every other k)
 // k_round_sweep: `blocks` workgroups of 256 threads sweep the tiles; 0 = one wave per tile.

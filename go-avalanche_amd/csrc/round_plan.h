@@ -13,6 +13,7 @@ enum class RoundKernel : int {
   Sweep,     // k_round_sweep (uncapped, k <= 8)
   Node,      // k_round_node (capped, k <= 8)
   FirstGen,  // k_round_fast / k_round_capped (any k; responder variants, non-polling nodes, A/B)
+  Lossy,     // k_round_lossy (uncapped, any k): lost Responses and unresponsive nodes (rule R5)
 };
 
 // The sweep kernel's build, as far as the records decide it. The launcher (sweep_kernel.h
@@ -30,6 +31,10 @@ struct PlanShape {
   bool has_comm;  // an RCCL communicator exchanges the rows
   int32_t pub_mode;
   bool any_nopoll;
+  // rule R5 (av_set_loss, av_set_responding): some Response of a sim round may be lost (a loss
+  // threshold above 0 or a node marked not responding); loss_neutral: a lost Response arrives with
+  // neutral votes (AV_LOSS_NEUTRAL) instead of not at all
+  bool lossy = false, loss_neutral = false;
 };
 
 // the options the decision reads (av_set_option)
@@ -45,7 +50,8 @@ struct PlanKnobs {
 };
 
 struct RoundPlan {
-  // responder variant 2 or non-polling nodes on a capped engine: no kernel runs them
+  // responder variant 2 or non-polling nodes on a capped engine, or a lossy round (R5) of a capped
+  // engine, of responder variant 2 or of a peer-push engine: no kernel runs them
   bool unsupported;
   RoundKernel kernel;
   SweepMode mode;  // kernel == Sweep
@@ -74,6 +80,8 @@ struct RoundPlan {
   // calm tiles (kernels.h calm): a klazy sweep round at k = 8 whose tiles may be left stale (vv, not
   // the uniform-only form) flags them kVCalm and takes flagged tiles as settled candidates
   bool calm;
+  // a sim round under R5 (kernel == Lossy); loss_neutral: its lost Responses shift in consider = 0
+  bool lossy, loss_neutral;
 };
 
 struct RecordFacts {
@@ -194,7 +202,13 @@ struct RecordFacts {
     uni_ok[out_buf] = p.uni_rows;
     // (every other kind of round: non-klazy, replay, capped, first-generation, an engine with an exchange)
     nq_ok = p.net_quiet_out;
-    if (p.replay)
+    if (p.lossy) {
+      // a skipped Response leaves a record short of 8 new votes, a neutral one shifts in consider = 0
+      // (vote.go:56); the round tags no snapshot buffer
+      snapshot_written();
+      warm_all = false;
+      if (p.loss_neutral) c_monotone = false;
+    } else if (p.replay)
       warm_all = false;
     else if (c_monotone && p.k >= 8 && !p.capped && all_valid)
       warm_all = true;  // every live record was polled and shifted in 8 considered votes
@@ -247,6 +261,21 @@ inline RoundPlan plan_round(const RecordFacts& f, const PlanShape& s, const Plan
   r.net_quiet_out = o.quiet_tiles && o.net_quiet && r.klazy && sweep && !o.count_changed && s.peer_world <= 1 && !s.has_comm;
   r.net_quiet_in = r.net_quiet_out && f.nq_ok;
   r.calm = o.calm_tiles && r.klazy && r.vv && !r.vv_uniform && s.k == 8 && sweep;
+  // R5: a sim round with lost Responses runs k_round_lossy on the stored planes alone; it neither
+  // reads nor leaves a deferred form, so the write-back rules above see none of them planned. Replay
+  // rounds ignore the setting (their stream carries its own neutral votes).
+  if (s.lossy && !replay) {
+    r.lossy = true;
+    r.loss_neutral = s.loss_neutral;
+    r.unsupported = r.unsupported || s.capped || s.pub_mode == 2 || s.peer_world > 1;
+    r.kernel = RoundKernel::Lossy;
+    r.mode = SweepMode::Check;
+    r.fresh = r.warm = r.vv = r.vv_uniform = r.klazy = r.kconsume = r.calm = false;
+    r.ref_rows = r.uni_rows = r.net_quiet_out = r.net_quiet_in = false;
+    r.wb_votes = f.v_stale;
+    r.wb_counts = f.k_pend;
+    r.wb_cpreset = f.c_preset;
+  }
   return r;
 }
 

@@ -160,6 +160,13 @@ class Engine {
   // transaction when it appears): the catalog slot, then one av_admit_targets call. Returns the
   // Processors that created a record (0: invalid target, catalog full, or every node holds it).
   int64_t AddTargetToReconcileAll(const Target& t);
+  // Lost Responses in the batched rounds (av_set_loss): each Response is lost with probability
+  // loss_threshold / 2^32; neutral = false: it never reaches RegisterVotes (processor.go:66-76),
+  // true: it arrives with a negative err for every vote (vote.go:55-56).
+  void SetLoss(uint32_t loss_threshold, bool neutral = false);
+  // Whether these nodes answer queries in the batched rounds (av_set_responding); they still poll.
+  void SetResponding(const std::vector<NodeID>& nodes, bool responds);
+  int64_t LostResponses() const;
   // Batched rounds for every node (the hot path).
   void RunRounds(int32_t rounds);
   int64_t Round() const;

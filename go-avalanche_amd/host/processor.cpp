@@ -119,6 +119,20 @@ int64_t Engine::AddTargetToReconcileAll(const Target& t) {
   return added;
 }
 
+void Engine::SetLoss(uint32_t loss_threshold, bool neutral) {
+  check(av_set_loss(h_, loss_threshold, neutral ? AV_LOSS_NEUTRAL : AV_LOSS_SKIP));
+}
+
+void Engine::SetResponding(const std::vector<NodeID>& nodes, bool responds) {
+  check(av_set_responding(h_, nodes.data(), (int64_t)nodes.size(), responds ? 1 : 0));
+}
+
+int64_t Engine::LostResponses() const {
+  int64_t n = 0;
+  check(av_lost_responses(h_, &n));
+  return n;
+}
+
 void Engine::RunRounds(int32_t rounds) {
   SyncValidity();
   check(av_run_rounds(h_, rounds));

@@ -33,6 +33,7 @@ STATUS_INVALID, STATUS_REJECTED, STATUS_ACCEPTED, STATUS_FINALIZED = 0, 1, 2, 3
 PEERS_RANDOM, PEERS_ROUND_ROBIN = 0, 1
 INIT_NONE, INIT_REJECTED, INIT_ACCEPTED, INIT_BERNOULLI, INIT_PAIRS = 0, 1, 2, 3, 4
 INIT_GIVEN = 5  # av_admit_targets only: acceptance from the caller's accepted[]
+LOSS_SKIP, LOSS_NEUTRAL = 0, 1  # av_set_loss: a lost Response registers nothing / neutral votes
 ABSENT_WORD = 0xFFFE0000
 FINALIZATION_SCORE = 128
 MAX_ELEMENT_POLL = 4096
@@ -103,6 +104,7 @@ EXPORTED = [
     "av_add_targets_batch", "av_admit_targets",
     "av_catalog_intern", "av_catalog_find", "av_catalog_find_device", "av_catalog_hashes", "av_catalog_retire",
     "av_register_votes_hashed",
+    "av_set_loss", "av_set_responding", "av_sample_lost", "av_lost_responses",
 ]
 
 _lib = None
@@ -190,6 +192,10 @@ def lib():
         "av_catalog_hashes": (i32, [_vp, _vp, _vp]),
         "av_catalog_retire": (i32, [_vp, _vp, i64, i32, _vp]),
         "av_register_votes_hashed": (i32, [_vp, i64, _vp, _vp, _vp, _vp, _vp]),
+        "av_set_loss": (i32, [_vp, u32, i32]),
+        "av_set_responding": (i32, [_vp, _vp, i64, i32]),
+        "av_sample_lost": (i32, [_vp, i64, i64, i64, _vp]),
+        "av_lost_responses": (i32, [_vp, P(i64)]),
     }
     for name, (res, args) in sig.items():
         if name == "av_net_quiet_rounds" and os.environ.get("AVHIP_LIB") and not hasattr(L, name):
@@ -527,6 +533,28 @@ class Engine:
     def set_polling(self, node, polls):
         """Whether `node` polls in the rounds (the example's loop returns, main.go:160-162)."""
         _check(lib().av_set_polling(self._h, node, int(bool(polls))))
+
+    def set_loss(self, threshold, mode=LOSS_SKIP):
+        """From the next round on, each Response is lost with probability threshold / 2**32 (rule R5:
+        av_set_loss). LOSS_SKIP: it registers nothing; LOSS_NEUTRAL: it registers neutral votes."""
+        _check(lib().av_set_loss(self._h, int(threshold), int(mode)))
+
+    def set_responding(self, nodes, responds):
+        """Whether `nodes` (global ids of the whole network) answer queries; set on every shard."""
+        nd = np.ascontiguousarray(np.atleast_1d(nodes), np.int64)
+        _check(lib().av_set_responding(self._h, _ptr(nd) if nd.size else None, nd.size, int(bool(responds))))
+
+    def sample_lost(self, rnd, n0=0, n1=None):
+        """The device's lost Responses of nodes [n0, n1) in round rnd: uint8[n1 - n0, k], 1 = lost."""
+        n1 = self.n_nodes if n1 is None else n1
+        out = np.zeros((n1 - n0, self.k), np.uint8)
+        _check(lib().av_sample_lost(self._h, rnd, n0, n1, _ptr(out)))
+        return out
+
+    def lost_responses(self):
+        out = C.c_int64(0)
+        _check(lib().av_lost_responses(self._h, C.byref(out)))
+        return out.value
 
     @property
     def round(self):

@@ -290,6 +290,45 @@ int av_get_round(av_engine* e, int64_t node, int64_t* out);
 int av_set_polling(av_engine* e, int64_t node, int32_t polls);
 int av_set_round(av_engine* e, int64_t node, int64_t round);
 
+/* ---- lost Responses and unresponsive nodes (harness rule R5) ----
+ * av_run_rounds otherwise simulates a perfect network: each of the k peers a
+ * node draws answers, with 0 or 1 for every target. The reference has two
+ * behaviours such rounds never exercise. RegisterVotes returns before it reads
+ * a vote when the query is unknown or expired (processor.go:66-76,
+ * AvalancheRequestTimeout avalanche.go:19-21): with that check disabled, a
+ * Response that does not arrive is a call that never happens. And a vote whose
+ * err is negative shifts consider = 0 into the window (vote.go:55-56).
+ * The Response of slot s of node n in engine round r is lost iff
+ * x[s & 3] < loss_threshold, x = philox4x32-10(ctr = {n, r, s >> 2, 6}, key =
+ * seed), or its peer (R1's draw, unchanged) is marked not responding. Neither
+ * depends on the target: target shards agree with the whole network.
+ *   AV_LOSS_SKIP: slot s registers nothing: no window shifts, no update, not
+ *     counted by av_applied_votes; later slots proceed and keep their own slot
+ *     index in their updates.
+ *   AV_LOSS_NEUTRAL: the Response arrives with err = 0x80000000 for every
+ *     polled target: both windows shift a 0, it counts as applied and follows
+ *     vote.go:58-75 literally.
+ * A Byzantine peer is lost like any other; a node that does not respond still
+ * polls (av_set_polling decides that); replay rounds ignore the setting (their
+ * stream carries its own neutral votes). With loss_threshold 0 and every node
+ * responding the engine plans, launches and computes what it did before.
+ * AV_ERR_UNSUPPORTED: a lossy round of an engine with M > 4096 or of responder
+ * variant 2 (from av_run_rounds, nothing changed), and the peer-push exchange
+ * (from av_set_loss, av_set_responding(.., 0), av_peer_init and
+ * av_peer_group_serial, up front). RCCL node shards and target shards work. */
+#define AV_LOSS_SKIP 0
+#define AV_LOSS_NEUTRAL 1
+/* P(lost) = loss_threshold / 2^32; takes effect from the next round. */
+int av_set_loss(av_engine* e, uint32_t loss_threshold, int32_t mode);
+/* Whether nodes[0..n) (global ids of the whole network, local or not) answer
+ * queries (default 1); like av_set_valid, set on every shard. */
+int av_set_responding(av_engine* e, const int64_t* nodes, int64_t n, int32_t responds);
+/* Device loss dump: [n1-n0][k], 1 = the Response of that slot of `round` is
+ * lost, for either reason (a parity dump, as av_sample_peers is of R1). */
+int av_sample_lost(av_engine* e, int64_t round, int64_t n0, int64_t n1, uint8_t* out);
+/* Lost Responses of polling local nodes since creation, one per (node, slot). */
+int av_lost_responses(av_engine* e, int64_t* out);
+
 /* ---- outputs ---- */
 int av_updates_count(av_engine* e, int64_t* n);
 /* Whether the device StatusUpdate log overflowed since the last fetch/discard

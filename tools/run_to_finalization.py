@@ -4,12 +4,18 @@
 per-round kernel throughput.
 
     python tools/run_to_finalization.py --workload c3 [--max-rounds 512] [--json out.json] [--census]
+                                        [--loss P] [--loss-mode skip|neutral] [--down F]
 
 --census adds, per round and from one Engine.census() call over the honest nodes: the targets on
 which no honest node holds a live record, the honest nodes that hold none at all (the example's
 "fully finalized" nodes, main.go:143-162), and the minimum over targets of the larger of the two
 accepted-side node counts (nodes holding the target accepted, nodes that finalized it accepted):
 how far the least advanced target's acceptance has got.
+
+--loss P loses each Response with probability P (rule R5, av_set_loss), --loss-mode says what a lost
+Response does (skip: it never arrives; neutral: it arrives with neutral votes), --down F marks a
+fraction F of the nodes, evenly spread, as not responding (av_set_responding). Defaults: a perfect
+network. The report then carries the lost Responses per round.
 """
 import argparse
 import json
@@ -35,6 +41,9 @@ def main():
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0xA7A1A9C4)
     ap.add_argument("--json", default=None)
     ap.add_argument("--census", action="store_true", help="per-round network census (see above)")
+    ap.add_argument("--loss", type=float, default=0.0, help="probability that a Response is lost")
+    ap.add_argument("--loss-mode", default="skip", choices=["skip", "neutral"])
+    ap.add_argument("--down", type=float, default=0.0, help="fraction of the nodes that do not respond")
     args = ap.parse_args()
     n, m, k, init_mode, init_param, byz, replay, desc = WORKLOADS[args.workload]
     assert not replay
@@ -43,12 +52,22 @@ def main():
     log_cap = min(2 * n * m + (1 << 20), 1 << 31)
     e = avhip.Engine(n, m, k=k, seed=args.seed, byz_threshold=byz, log_capacity=log_cap)
     e.init_records(init_mode, init_param)
+    lossy = args.loss > 0 or args.down > 0
+    if args.loss > 0:
+        e.set_loss(min(int(args.loss * 2**32), 2**32 - 1),
+                   avhip.LOSS_NEUTRAL if args.loss_mode == "neutral" else avhip.LOSS_SKIP)
+    elif args.down > 0:
+        e.set_loss(0, avhip.LOSS_NEUTRAL if args.loss_mode == "neutral" else avhip.LOSS_SKIP)
+    n_down = int(args.down * n)
+    if n_down:
+        e.set_responding(np.arange(n_down, dtype=np.int64) * n // n_down, 0)
     honest_records = e.live_records(honest_only=True)
     per_round = []
     t_start = time.perf_counter()
     done_round = None
     for r in range(args.max_rounds):
         a0, f0 = e.applied_votes(), e.finalized_count()
+        l0 = e.lost_responses() if lossy else 0
         e.set_timing(True)
         e.run_rounds(1)
         ms, _ = e.kernel_stats()
@@ -58,6 +77,8 @@ def main():
         live = e.live_records(honest_only=True)
         per_round.append({"round": r, "kernel_ms": ms, "applied": e.applied_votes() - a0,
                           "finalized": e.finalized_count() - f0, "emitted": emitted, "honest_live": live})
+        if lossy:
+            per_round[-1]["lost"] = e.lost_responses() - l0
         if args.census:
             c = e.census(honest_only=True, count_sum=False, hist=False)
             tc, nc = c["target_classes"], c["node_classes"]
@@ -82,6 +103,8 @@ def main():
         "rounds_run": len(per_round),
         "honest_live_at_end": per_round[-1]["honest_live"],
         "applied_votes": total_applied,
+        **({"loss": args.loss, "loss_mode": args.loss_mode, "nodes_down": n_down,
+            "lost_responses": e.lost_responses()} if lossy else {}),
         "kernel_ms_total": kern,
         "updates_per_s_kernel": total_applied / (kern * 1e-3) if kern else None,
         "wall_s": wall,
