@@ -21,10 +21,45 @@ again before each one. In a *taken* seed (honest, k = 8) the rounds flagged
 the deferring engine must move fewer bytes than its plain twin. Seeds with
 k < 8 plan none of the deferred forms (plan_round asks k == 8 for vv, klazy,
 reference and uniform rows) and Byzantine seeds never settle, so neither
-carries taken rounds."""
+carries taken rounds.
+
+Lossy lives (make_lossy_schedule, N_LOSSY_SEEDS of them; rule R5) are lives of
+the same kind, drawn from a generator of their own, with loss laid over them.
+Their seed mix is lossy_config's: k = 12 once, k in {1, 3, 5} three times, three
+Byzantine seeds, the rest honest at k = 8. Three more ops:
+  set_loss (thr, mode) / set_responding (nodes, responds): av_set_loss and
+  av_set_responding on every engine; observe with what = "lost": av_sample_lost
+  of the round about to run against lossy_ref.lost_table, and av_lost_responses.
+While the threshold is non-zero or a node is down, Life runs each sim round
+through lossy_ref.LossyRef.round instead of Sim.run_round; a replay round is
+the plain one whatever the loss state and loses nothing.
+The overlay (_overlay) lays one to three stretches [a, b) of 2-8 rounds, at
+least 3 rounds apart, over the schedule. A stretch opens before round a, ahead
+of that round's disturbances, with set_loss and/or set_responding(.., 0), and
+closes before round b with set_loss(0) and set_responding(.., 1). Modes and
+probabilities: SKIP {0.10, 0.25, 0.60}, NEUTRAL {0.05, 0.15}; with nodes down
+the threshold is sometimes 0; one seed's first stretch has threshold 2^32 - 1.
+Down sets by (seed + stretch) mod 4: none, a few nodes, nodes 0 and n - 1, one
+whole 32-node word of the bitset; one seed's first stretch starts with one
+round of every node down. A stretch of 3 rounds or more may change part-way:
+SKIP <-> NEUTRAL, a node back up, one more down. A stretch that starts in
+phase 1 is SKIP throughout (a NEUTRAL round clears c_monotone). Each stretch is
+laid over a disturbance of the kind WANTED names for it (or the replay round)
+where the life has one, else late in the life, where records finalize. rounds
+steps are cut at every stretch edge and change and keep their route and digest
+range. A taken flag is cleared in [a, b + 2): a lossy round defers nothing, and
+the plain round after it runs in the check form and only sets warm_all again.
+In a taken seed the first stretch is, where the life has room for one, a phase-1
+SKIP stretch ending at a b with no disturbance in b - 2 .. b + 2 (no re-init in
+b - 9 .. b) and c_monotone kept through b + 2; if the options then in force let plan_round defer (kernel 2
+and virtual_votes, or count_lazy with count_bound < 120), round b + 2 runs as a
+step of its own, flagged taken and "regain": the engine must be deferring
+again. tests/test_life_schedule_cpu.py checks on the oracle that rows are
+identical and targets valid at b, b + 1 and b + 2."""
 import numpy as np
 
 from census_ref import census_from_words
+from lossy_ref import LossyRef, lost_table
 
 N_SEEDS = 32
 INIT_ACCEPTED, INIT_BERNOULLI, INIT_PAIRS = 2, 3, 4
@@ -73,10 +108,14 @@ def seed_config(seed):
 
 
 class _Gen:
-    def __init__(self, seed):
-        self.rng = rng = np.random.default_rng(0x11FE0000 + seed)
-        self.n, self.m, self.byz, small_k = seed_config(seed)
-        self.k = int(rng.choice([3, 5])) if small_k else 8
+    def __init__(self, seed, rng=None, config=None):
+        """rng, config = (n, m, byz, k): the lossy lives' own generator and seed mix."""
+        self.rng = rng = np.random.default_rng(0x11FE0000 + seed) if rng is None else rng
+        if config is None:
+            self.n, self.m, self.byz, small_k = seed_config(seed)
+            self.k = int(rng.choice([3, 5])) if small_k else 8
+        else:
+            self.n, self.m, self.byz, self.k = config
         self.taken_seed = self.byz == 0 and self.k == 8
         self.values = option_values(self.k)
         self.off_used = set()
@@ -184,7 +223,12 @@ class _Gen:
 
 
 def make_schedule(seed):
-    g = _Gen(seed)
+    return _build(_Gen(seed), seed, 7000 + seed)[0]
+
+
+def _build(g, seed, engine_seed):
+    """The schedule of generator g, and what the lossy overlay needs to know of it: the disturbance
+    steps per round, their kinds [(round, kind)] and the replay round."""
     rng, n, m, k = g.rng, g.n, g.m, g.k
     # INIT_PAIRS starts every target at an even split, which an honest network of these sizes leaves only
     # after 9-24 rounds: too late for settled stretches inside phase 1, so the taken seeds draw the others
@@ -197,11 +241,13 @@ def make_schedule(seed):
     initial = g.draw_options(False, fixed=[flat[i] for i in (seed % N_SEEDS, seed % N_SEEDS + N_SEEDS) if i < len(flat)])
 
     at = {}  # round index -> disturbance steps run before that round
+    kinds = []  # (round, kind) of every disturbance
     alone = set()  # rounds that run as a step of their own (the taken rounds)
     taken = {}  # taken round -> the deferral options on in that round
 
     def place(r, kind, phase2):
         last = r
+        kinds.append((r, kind))
         for off, step in g.disturbance(kind, phase2):
             rr = min(r + off, rounds - 1)
             at.setdefault(rr, []).append(step)
@@ -241,6 +287,7 @@ def make_schedule(seed):
         # disturb before the next disturbance (at most 7 rounds on), so the records are re-initialised too
         if g.taken_seed and kind != "reinit" and not g.current["virtual_votes"] and bound_at(last + 6) >= 120:
             at[r].append(dict(op="reinit"))
+            kinds.append((r, "reinit"))
             kind, bound, bound_r = "reinit", -6, r
         # a re-initialised network converges anew first
         r = last + (int(rng.integers(5, 8)) + (5 if kind == "reinit" else 0) if spaced else int(rng.integers(1, 5)))
@@ -275,9 +322,204 @@ def make_schedule(seed):
             steps.append(g.observation())
     steps.append(dict(op="observe", what="read_full"))
     steps.append(dict(op="observe", what="pref"))
-    return dict(seed=seed, n=n, m=m, k=k, engine_seed=7000 + seed, byz=g.byz, init_mode=init_mode,
-                init_param=init_param, rounds=rounds, phase1=phase1, taken_seed=g.taken_seed, options=initial,
-                steps=steps)
+    sched = dict(seed=seed, n=n, m=m, k=k, engine_seed=engine_seed, byz=g.byz, init_mode=init_mode,
+                 init_param=init_param, rounds=rounds, phase1=phase1, taken_seed=g.taken_seed, options=initial,
+                 steps=steps)
+    return sched, dict(at=at, kinds=kinds, replay_at=replay_at)
+
+
+# ---- lossy lives: a life of the kind above with loss stretches laid over it
+N_LOSSY_SEEDS = 16
+LOSS_SKIP, LOSS_NEUTRAL = 0, 1
+SKIP_P, NEUTRAL_P = (0.10, 0.25, 0.60), (0.05, 0.15)
+THR_MAX = 2**32 - 1
+DOWN_KINDS = ("none", "few", "ends", "word")  # and "all", once
+LOSSY_K = {5: 12, 2: 3, 9: 5, 13: 1}  # seed -> k; every other seed k = 8
+LOSSY_BYZ = (3, 7, 11)
+THR_MAX_SEED, ALL_DOWN_SEED = 3, 9  # whose first stretch loses (nearly) every draw / starts with every node down
+# the disturbance a stretch is laid over, by (3 * seed + stretch) mod len: every kind meets a lossy round
+WANTED = ("register", "reinit", "write", "replay", "add", "options", "neutral", "kernel_flip", "register_batch",
+          "replay", "set_valid", "reinit", "materialize")
+
+
+def lossy_config(seed):
+    """Shape, Byzantine share and k of a lossy seed."""
+    n, m = SHAPES[seed % len(SHAPES)]
+    return n, m, (BYZ20 if seed in LOSSY_BYZ else 0), LOSSY_K.get(seed, 8)
+
+
+def make_lossy_schedule(seed):
+    g = _Gen(seed, np.random.default_rng(0x105E0000 + seed), lossy_config(seed))
+    sched, info = _build(g, seed, 7100 + seed)
+    return _overlay(g, sched, info)
+
+
+def _overlay(g, sched, info):
+    """One to three loss stretches [a, b) of 2-8 rounds over the schedule: set_loss / set_responding
+    steps before round a (ahead of that round's disturbances), changes part-way, the closing steps
+    before round b; rounds steps cut at every such edge; taken flags cleared in [a, b + 2); regain
+    rounds flagged (module docstring)."""
+    rng, n, seed = g.rng, g.n, sched["seed"]
+    rounds, phase1 = sched["rounds"], sched["phase1"]
+    at, kinds, replay_at = info["at"], info["kinds"], info["replay_at"]
+    dist = sorted(at)
+    reinits = [r for r in dist if any(s["op"] == "reinit" for s in at[r])]
+    first_break = min([r for r in dist if any(breaks_c_monotone(s) for s in at[r])] + [replay_at])
+
+    def settled_end(b):
+        """A stretch ending at b may be followed by a regain round: nothing disturbs b - 2 .. b + 2 (a
+        re-init: b - 9 ..), and c_monotone holds through b + 2."""
+        return (b + 2 < min(first_break, rounds) and not any(b - 2 <= d <= b + 2 for d in dist) and
+                not any(b - 9 <= d <= b for d in reinits))
+
+    def deferring_at(x):
+        """The deferral options on in round x if plan_round can defer there (kernel 2, and virtual_votes
+        or count_lazy with RecordFacts::count_bound < 120), else None."""
+        cur = dict(DEFAULTS)
+        cur.update({nm: v for nm, v in sched["options"] if nm in cur})
+        bound, bound_r = -6, 0
+        for r in dist:
+            if r > x:
+                break
+            for step in at[r]:
+                if step["op"] == "options":
+                    cur.update({nm: v for nm, v in step["set"] if nm in cur})
+                elif step["op"] == "reinit":
+                    bound, bound_r = -6, r
+                elif step["op"] in ("register", "register_batch"):
+                    bound, bound_r = min(127, bound + 8 * (r - bound_r) + max_node_votes(step)), r
+        lazy = cur["count_lazy"] and min(127, bound + 8 * (x - bound_r)) < 120
+        if cur["kernel"] == 2 and (cur["virtual_votes"] or lazy):
+            return [d for d in DEFERRALS if cur[d]]
+        return None
+
+    spans = []
+
+    def free(a, b):
+        return 1 <= a and a + 2 <= b <= rounds - 1 and all(b + 3 <= x or y + 3 <= a for x, y in spans)
+
+    def down_set(kind):
+        if kind == "few":
+            return sorted(set(rng.integers(0, n, size=int(rng.integers(1, 5))).tolist()))
+        if kind == "ends":
+            return [0, n - 1]
+        if kind == "word":  # one whole word of the responding bitset
+            w = int(rng.integers(0, n // 32))
+            return list(range(32 * w, 32 * w + 32))
+        return list(range(n)) if kind == "all" else []
+
+    def set_loss(thr, mode):
+        return dict(op="set_loss", thr=int(thr), mode=int(mode))
+
+    def set_responding(nodes, responds):
+        return dict(op="set_responding", nodes=np.array(nodes, np.int64), responds=int(responds))
+
+    def threshold(mode):
+        return int(float(rng.choice(NEUTRAL_P if mode == LOSS_NEUTRAL else SKIP_P)) * 2**32)
+
+    loss_steps, regain = {}, {}
+    for j in range(int(rng.integers(1, 4))):
+        length = int(rng.integers(2, 9))
+        a = b = None
+        ends = [x for x in range(12, phase1) if settled_end(x)] if g.taken_seed and j == 0 else []
+        if ends:  # a phase-1 SKIP stretch that a regain round follows: late, where records finalize
+            b = max(ends) if rng.random() < 0.5 else int(rng.choice(ends))
+            a = max(8, b - length)
+        else:
+            first = (3 * seed + j) % len(WANTED)
+            over = []
+            for want in (WANTED[first], "materialize") + WANTED[first + 1:]:  # (materialize: the rarest)
+                over = [replay_at] if want == "replay" else [r for r, kd in kinds if kd == want]
+                if over:
+                    break
+            if over:
+                d = int(rng.choice(over))
+                a = max(1, d - int(rng.integers(0, length)))
+                b = min(max(a + length, d + 1), rounds - 1)
+        for _ in range(8):
+            if a is not None and free(a, b):
+                break
+            a = int(rng.integers(14, rounds - 3))
+            b = min(a + length, rounds - 1)
+        else:
+            continue
+        spans.append((a, b))
+        # phase 1 holds SKIP stretches only: a NEUTRAL round clears c_monotone
+        mode = LOSS_SKIP if a < phase1 else int(rng.integers(0, 2))
+        kind = DOWN_KINDS[(seed + j) % len(DOWN_KINDS)]
+        thr = threshold(mode)
+        if kind != "none" and rng.random() < 0.25:
+            thr = 0  # only nodes are down
+        ev = {}
+        if j == 0 and seed == ALL_DOWN_SEED:  # one round with every node down, then an ordinary stretch
+            down = down_set("few")
+            ev[a] = [set_loss(0, mode), set_responding(down_set("all"), 0)]
+            ev[a + 1] = [set_responding(down_set("all"), 1), set_loss(thr or threshold(mode), mode),
+                         set_responding(down, 0)]
+        else:
+            if j == 0 and seed == THR_MAX_SEED:
+                thr = THR_MAX
+            down = down_set(kind)
+            ev[a] = ([set_loss(thr, mode)] if thr or mode else []) + ([set_responding(down, 0)] if down else [])
+            if b - a >= 3 and (rng.random() < 0.7 or a >= phase1):  # a change part-way
+                x = int(rng.integers(a + 1, b))
+                if a >= phase1 and rng.random() < 0.6:  # SKIP <-> NEUTRAL
+                    mode = 1 - mode
+                    thr = threshold(mode)
+                    ev[x] = [set_loss(thr, mode)]
+                elif down and (thr or len(down) > 1) and rng.random() < 0.5:  # a node comes back up
+                    up = down.pop(int(rng.integers(0, len(down))))
+                    ev[x] = [set_responding([up], 1)]
+                else:  # one more goes down
+                    more = int(rng.choice([i for i in range(n) if i not in down]))
+                    down.append(more)
+                    ev[x] = [set_responding([more], 0)]
+        ev[b] = [set_loss(0, LOSS_SKIP)] + ([set_responding(sorted(down), 1)] if down else [])
+        for x, steps in ev.items():
+            loss_steps.setdefault(x, []).extend(steps)
+        if ends:
+            on = deferring_at(b + 2)
+            if on is not None:
+                regain[b + 2] = on
+
+    cuts = set(loss_steps) | set(regain) | {x + 1 for x in regain}
+    out, pre = [], []
+
+    def with_observation(steps):
+        if rng.random() < 0.6:
+            lo, hi = sorted(rng.integers(0, n + 1, size=2).tolist())
+            lo = min(lo, n - 1)
+            steps = steps + [dict(op="observe", what="lost", n0=lo, n1=max(hi, lo + 1))]
+        return steps
+
+    for step in sched["steps"]:
+        if step["op"] not in ("rounds", "replay"):
+            pre.append(step)
+            continue
+        first = step["first"]
+        if first in loss_steps:  # ahead of the round's disturbances
+            i = next((i for i, s in enumerate(pre) if s["op"] != "observe"), len(pre))
+            pre[i:i] = with_observation(loss_steps.pop(first))
+        out += pre
+        pre = []
+        if step["op"] == "replay":
+            out.append(step)
+            continue
+        end = first + step["c"]
+        lo = first
+        for hi in sorted(x for x in cuts if first < x < end) + [end]:
+            piece = dict(step, c=hi - lo, first=lo)
+            if any(a <= lo < b + 2 for a, b in spans):  # a lossy round defers nothing; the plain round after it checks
+                piece.update(taken=False, deferrals=[])
+            if lo in regain:
+                piece.update(taken=True, deferrals=regain[lo], regain=True)
+            out.append(piece)
+            if hi < end and hi in loss_steps:
+                out += with_observation(loss_steps.pop(hi))
+            lo = hi
+    assert not loss_steps, loss_steps
+    out += pre
+    return dict(sched, steps=out, lossy=True, stretches=sorted(spans), regain=sorted(regain))
 
 
 PEER_REFUSED = frozenset(("register", "register_batch", "add", "write"))  # record writes a peer-push engine refuses
@@ -293,10 +535,11 @@ def restrict(sched, drop):
     return out
 
 
-def target_shards(seed):
+def target_shards(seed, m=None):
     """The target ranges of a seed's sharded life: 2, 3, 4 or 8 shards (at most one per 32-target
-    block) of whole blocks, balanced to within one block (avhip.sharding.target_shard)."""
-    m = seed_config(seed)[1]
+    block) of whole blocks, balanced to within one block (avhip.sharding.target_shard). m: the
+    targets of a life whose shape is not seed_config's (the lossy lives)."""
+    m = seed_config(seed)[1] if m is None else m
     blocks = (m + 31) // 32
     g = min(SHARD_COUNTS[seed % len(SHARD_COUNTS)], blocks)
     return [(32 * (r * blocks // g), min(32 * ((r + 1) * blocks // g), m)) for r in range(g)]
@@ -329,6 +572,8 @@ def breaks_c_monotone(step):
     """Whether the engine clears RecordFacts::c_monotone on this step (round_plan.h)."""
     if step["op"] in ("replay", "write"):
         return True
+    if step["op"] == "set_loss":  # a NEUTRAL lossy round shifts in consider = 0
+        return step["mode"] == LOSS_NEUTRAL
     if step["op"] in ("register", "register_batch"):
         return bool(np.any(step["errs"] >= np.uint32(0x80000000)))
     return step["op"] == "options" and ("warm_skip", 0) in [tuple(x) for x in step["set"]]
@@ -348,7 +593,9 @@ class Life:
     def __init__(self, sched, cabi, engines=None, av=None):
         self.s, self.cabi, self.engines, self.av = sched, cabi, dict(engines or {}), av
         self.valid = np.ones(sched["m"], bool)
+        self.thr, self.mode = 0, LOSS_SKIP  # the loss state; the down set is the reference's (self.ref.down)
         self.sim = self._new_sim(0)
+        self.ref = self._new_ref(None)
         self.byz = np.array([self.sim.is_byzantine(j) for j in range(sched["n"])], bool)
         self.applied = self.finalized = 0
         self.options = {name: dict() for name in self.engines}
@@ -356,6 +603,7 @@ class Life:
         self.where = ""
         self.round_hook = None  # called as (round index, sim, valid) before every sim round
         self.post_init = {}  # engine name -> options set again after every av_init_records
+        self.lossy_rows = []  # the update rows of every lossy round
 
     def _new_sim(self, first_round):
         s = self.s
@@ -365,6 +613,19 @@ class Life:
         for t in np.flatnonzero(~self.valid):
             sim.set_valid(int(t), False)
         return sim
+
+    def _new_ref(self, old):
+        """The lossy reference round over the current Sim; the down set and the counters carry over, and
+        its validity is the life's own array."""
+        ref = LossyRef(self.sim, self.s["engine_seed"])
+        ref.valid = self.valid
+        if old is not None:
+            ref.down, ref.applied, ref.lost = old.down, old.applied, old.lost
+        return ref
+
+    def lossy(self):
+        """The engine's lossy(): the next sim round may lose a Response."""
+        return self.thr != 0 or bool(self.ref.down)
 
     def set_options(self, name, opts):
         for nm, v in opts:
@@ -410,7 +671,13 @@ class Life:
             for _ in range(step["c"]):
                 if self.round_hook:
                     self.round_hook(sim.round, sim, self.valid)
-                out.append(sim.run_round())
+                if self.lossy():
+                    before_applied = self.ref.applied
+                    rows = self.ref.round(self.thr, self.mode)
+                    out.append((rows, self.ref.applied - before_applied))
+                    self.lossy_rows.append(rows)
+                else:
+                    out.append(sim.run_round())
             for e in self.engines.values():
                 e.run_rounds(step["c"])
         exp = np.concatenate([u for u, _ in out]) if out else np.zeros((0, 5), np.int64)
@@ -425,8 +692,14 @@ class Life:
         n, m = s["n"], s["m"]
         dump = sim.dump()
         live = (dump >> np.uint32(17)) < 128
+        if what == "lost":  # the draw of the round about to run, and the Responses lost so far
+            lost = lost_table(s["engine_seed"], n, s["k"], sim.round, self.thr, self.ref.down)
         for name, e in self.engines.items():
-            if what == "read_full":
+            if what == "lost":
+                n0, n1 = ob["n0"], ob["n1"]
+                self._same(e.sample_lost(sim.round, n0, n1), lost[n0:n1].astype(np.uint8), name, "sample_lost")
+                self._same(e.lost_responses(), self.ref.lost, name, "lost_responses")
+            elif what == "read_full":
                 self._same(e.read_records(), dump, name, "read_records")
             elif what == "read_rect":
                 n0, n1, t0, t1 = ob["n0"], ob["n1"], ob["t0"], ob["t1"]
@@ -506,6 +779,7 @@ class Life:
             first = sim.round
             sim.close()
             self.sim = self._new_sim(first)
+            self.ref = self._new_ref(self.ref)
             for name, e in E.items():
                 e.discard_updates()
                 e.init_records(s["init_mode"], s["init_param"])
@@ -513,6 +787,14 @@ class Life:
         elif op == "options":
             if "test" in E:
                 self.set_options("test", step["set"])
+        elif op == "set_loss":
+            self.thr, self.mode = step["thr"], step["mode"]
+            for e in E.values():
+                e.set_loss(step["thr"], step["mode"])
+        elif op == "set_responding":
+            self.ref.set_responding(step["nodes"], step["responds"])
+            for e in E.values():
+                e.set_responding(step["nodes"], step["responds"])
         elif op == "write":
             sim.write_records(step["words"], step["n0"], step["t0"])
             for e in E.values():

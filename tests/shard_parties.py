@@ -199,6 +199,22 @@ class _Party:
         for e in self.engines:  # every shard, not only the owner
             e.set_valid(target, valid)
 
+    def set_loss(self, threshold, mode=0):
+        for e in self.engines:
+            e.set_loss(threshold, mode)
+
+    def set_responding(self, nodes, responds):
+        for e in self.engines:  # global node ids, on every shard
+            e.set_responding(nodes, responds)
+
+    def sample_lost(self, rnd, n0=0, n1=None):
+        tables = [e.sample_lost(rnd, n0, n1) for e in self.engines]
+        assert all(np.array_equal(t, tables[0]) for t in tables[1:]), "sample_lost differs between the shards"
+        return tables[0]
+
+    def lost_responses(self):
+        return _common([e.lost_responses() for e in self.engines], "lost_responses")
+
     def updates_digest(self, n0=None, n1=None):
         return merge_digests([e.updates_digest(n0, n1) for e in self.engines])
 

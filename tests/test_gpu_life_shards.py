@@ -7,6 +7,10 @@ shard_parties.TargetShards. Every call takes global ids, so an engine that is of
 target_begin anywhere (drop-in votes, add_targets, validity, cells, poll sets, rectangles,
 replay slices, the compact header) differs from the oracle at that step.
 
+test_life_target_shards_lossy: the lossy lives (life_schedule.make_lossy_schedule) on their target
+shards; set_loss and set_responding go to every shard, and every shard must count the same lost
+Responses.
+
 test_life_peer_group: the schedules without the record writes a peer-push engine refuses, on
 serial peer groups of 2, 4 or 8 ranks (shard_parties.PeerGroup) in the masked, full and direct
 exchange modes: validity flips, materialize, option and kernel switches, re-inits and a replay
@@ -69,6 +73,7 @@ def run_life(oracle, sched, make_party, kind, first_options=()):
         assert p.applied_votes() == life.applied, (seed, name, "applied_votes")
         assert p.finalized_count() == life.finalized, (seed, name, "finalized_count")
         assert p.round == sched["rounds"]
+        assert p.lost_responses() == life.ref.lost, (seed, name, "lost_responses")
         p.close()
 
 
@@ -78,6 +83,16 @@ def test_life_target_shards(oracle, seed):
     ranges = ls.target_shards(seed)
     run_life(oracle, sched, lambda: sp.TargetShards([new_engine(sched, target_range=r) for r in ranges], ranges, avhip),
              "target")
+
+
+@pytest.mark.parametrize("seed", range(ls.N_LOSSY_SEEDS))
+def test_life_target_shards_lossy(oracle, seed):
+    """The lossy lives on target shards: every shard runs the whole network's loss (the draw depends on
+    node, round and slot, and on the peer alone), so the shards' lost_responses must be equal."""
+    sched = ls.make_lossy_schedule(seed)
+    ranges = ls.target_shards(seed, sched["m"])
+    run_life(oracle, sched, lambda: sp.TargetShards([new_engine(sched, target_range=r) for r in ranges], ranges, avhip),
+             "lossy target")
 
 
 @pytest.mark.parametrize("seed", [s for s in range(ls.N_SEEDS) if ls.peer_world(s) is not None])
