@@ -160,14 +160,15 @@ __global__ __launch_bounds__(256) void k_dropin_keys(const DropInParams p, uint3
 }
 }  // namespace
 
-hipError_t launch_dropin_keys(const DropInParams& p, uint32_t* keys, uint32_t* vidx, uint32_t* info, hipStream_t s) {
+hipError_t launch_dropin_keys(const DropInParams& p, const GroupScratch& g, hipStream_t s) {
   if (!p.n_resp) return hipSuccess;
-  hipLaunchKernelGGL(k_dropin_keys, dim3(std::min<uint32_t>(p.n_resp, 65535u)), dim3(256), 0, s, p, keys, vidx, info);
+  hipLaunchKernelGGL(k_dropin_keys, dim3(std::min<uint32_t>(p.n_resp, 65535u)), dim3(256), 0, s, p, g.keys, g.vidx,
+                     g.info);
   return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------
-// Drop-in RegisterVotes batch (engine_records.cpp av_register_votes_batch): group the votes by lane (node,
+// Drop-in RegisterVotes batch (engine_dropin.cpp group_by_lane): group the votes by lane (node,
 // 32-target block) keeping their order inside a lane — the stable radix sort of (lane, position) —
 // then run-length encode the sorted lanes into the (lanes, offs) CSR k_register_votes walks.
 // ---------------------------------------------------------------------------
@@ -207,21 +208,20 @@ uint64_t group_votes_scratch_words(uint32_t n) {
   return std::max<uint64_t>(dscan::radix_scratch_words(n), (uint64_t)n + 1u + dscan::scan_scratch_words((uint64_t)n + 1u));
 }
 
-hipError_t launch_group_votes(uint64_t* scratch, const uint32_t* keys, const uint32_t* vidx, const uint32_t* info,
-                              uint32_t n, int key_bits, uint32_t* keys_s, uint32_t* perm_s, uint32_t* keys_t,
-                              uint32_t* perm_t, uint32_t* lanes, uint32_t* offs, uint32_t* n_runs, uint32_t* entries,
-                              hipStream_t s) {
-  if (n == 0) return hipMemsetAsync(n_runs, 0, 4, s);
-  hipError_t e = dscan::launch_radix_sort_pairs(keys, nullptr, n, key_bits, keys_s, perm_s, keys_t, perm_t, scratch, s);
+hipError_t launch_group_votes(const GroupScratch& g, uint32_t n, int key_bits, hipStream_t s) {
+  if (n == 0) return hipMemsetAsync(g.nruns, 0, 4, s);
+  hipError_t e =
+      dscan::launch_radix_sort_pairs(g.keys, nullptr, n, key_bits, g.keys_s, g.perm_s, g.keys_t, g.perm_t, g.temp, s);
   if (e != hipSuccess) return e;
   // run index of every position: exclusive scan of the run heads (run_of[n] = runs)
-  uint64_t* run_of = scratch;
-  if ((e = dscan::launch_scan(HeadsIn{keys_s}, n, run_of, scratch + n + 1u, s)) != hipSuccess) return e;
-  const uint32_t g = (n + 255u) / 256u;
-  hipLaunchKernelGGL(k_rle_write, dim3(g), dim3(256), 0, s, (const uint32_t*)keys_s, (const uint64_t*)run_of, n,
-                     lanes, offs, n_runs);
+  uint64_t* run_of = g.temp;
+  if ((e = dscan::launch_scan(HeadsIn{g.keys_s}, n, run_of, g.temp + n + 1u, s)) != hipSuccess) return e;
+  const uint32_t grid = (n + 255u) / 256u;
+  hipLaunchKernelGGL(k_rle_write, dim3(grid), dim3(256), 0, s, (const uint32_t*)g.keys_s, (const uint64_t*)run_of, n,
+                     g.lanes, g.offs, g.nruns);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(k_vote_entries, dim3(g), dim3(256), 0, s, (const uint32_t*)perm_s, vidx, info, n, entries);
+  hipLaunchKernelGGL(k_vote_entries, dim3(grid), dim3(256), 0, s, (const uint32_t*)g.perm_s, (const uint32_t*)g.vidx,
+                     (const uint32_t*)g.info, n, g.entries);
   return hipGetLastError();
 }
 

@@ -1,7 +1,8 @@
 // Internal to the host side of libavhip.so (engine*.cpp): the error macros, the engine's state and the
 // helpers that cross its translation units. engine.cpp decides what a round launches and creates and
 // destroys engines; engine_peer.cpp holds the peer exchange, engine_log.cpp StatusUpdate delivery,
-// engine_records.cpp record I/O outside a round.
+// engine_records.cpp record I/O outside a round, engine_dropin.cpp the drop-in write batches (added
+// targets and votes, laid out by batch_layout.h), engine_catalog.cpp the Hash catalog.
 //
 // The host objects are compiled with hidden visibility: only what include/avhip.h declares is exported.
 #pragma once
@@ -404,6 +405,14 @@ inline int counter_query(av_engine* e, const void* out) {
   AV_ENTER(e);
   AV_PEER_SYNC_CHECK(e);
   AV_CHECK(out, AV_ERR_INVALID_ARG, "null argument");
+  return AV_OK;
+}
+
+// Peer-push engines keep every replica of a snapshot buffer identical; a
+// write to this rank's rows outside a round would break that.
+inline int peer_local_write_check(const av_engine* e) {
+  AV_CHECK(e->peer_world <= 1, AV_ERR_UNSUPPORTED,
+           "record writes outside a round are not supported on a peer-push node-sharded engine");
   return AV_OK;
 }
 

@@ -1,6 +1,6 @@
 // libavhip.so: the engine's Hash catalog (catalog.h). The caller's 64-bit hashes (avalanche.go:71)
 // are interned into the slots of the engine's target range on the host; the device holds a copy of
-// the table image that av_register_votes_hashed (engine_records.cpp) and av_catalog_find_device probe.
+// the table image that av_register_votes_hashed (engine_dropin.cpp) and av_catalog_find_device probe.
 #include <cstring>
 
 #include "engine.h"
@@ -88,20 +88,20 @@ int av_catalog_find_device(av_engine* e, const int64_t* hashes, int64_t n, int64
   AV_TRY(catalog_sync(e));
   if (n == 0) return AV_OK;
   const size_t m = (size_t)n;
-  AV_HIP(e->dropin_host.reserve(m * 12, avmem::Slack::kMiB, hipHostMallocDefault));
-  auto* hh = static_cast<int64_t*>(e->dropin_host.get());
-  auto* hp = reinterpret_cast<uint32_t*>(hh + m);
-  std::memcpy(hh, hashes, m * 8);
+  avlay::Carver size;
+  avlay::find_staging(size, m);
+  AV_HIP(e->dropin_host.reserve(size.bytes(), avmem::Slack::kMiB, hipHostMallocDefault));
   void* buf = nullptr;
-  AV_TRY(engine_scratch(e, m * 12 + 64, &buf));
-  auto* dh = static_cast<int64_t*>(buf);  // hipMalloc'ed: 256-byte aligned
-  auto* dp = reinterpret_cast<uint32_t*>(dh + m);
-  AV_HIP(hipMemcpyAsync(dh, hh, m * 8, hipMemcpyHostToDevice, e->stream));
-  AV_TRY(catalog_pack(e, dh, nullptr, nullptr, 0u, (uint32_t)n, dp, nullptr));
-  AV_HIP(hipMemcpyAsync(hp, dp, m * 4, hipMemcpyDeviceToHost, e->stream));
+  AV_TRY(engine_scratch(e, size.bytes(), &buf));
+  avlay::Carver host(e->dropin_host.get()), dev(buf);
+  const avlay::FindStaging h = avlay::find_staging(host, m), d = avlay::find_staging(dev, m);
+  std::memcpy(h.hashes, hashes, m * 8);
+  AV_HIP(hipMemcpyAsync(d.hashes, h.hashes, m * 8, hipMemcpyHostToDevice, e->stream));
+  AV_TRY(catalog_pack(e, d.hashes, nullptr, nullptr, 0u, (uint32_t)n, d.packed, nullptr));
+  AV_HIP(hipMemcpyAsync(h.packed, d.packed, m * 4, hipMemcpyDeviceToHost, e->stream));
   AV_HIP(hipStreamSynchronize(e->stream));
   for (size_t i = 0; i < m; ++i)
-    slots[i] = (hp[i] & avk::kDropUnknown) ? -1 : e->t0 + (int64_t)(hp[i] & avk::kDropTl);
+    slots[i] = (h.packed[i] & avk::kDropUnknown) ? -1 : e->t0 + (int64_t)(h.packed[i] & avk::kDropTl);
   return AV_OK;
 }
 

@@ -10,6 +10,7 @@
 
 #include <type_traits>
 
+#include "batch_layout.h"
 #include "catalog.h"
 
 namespace avk {
@@ -494,7 +495,7 @@ hipError_t launch_register_votes(const DropInParams& p, hipStream_t s);
 hipError_t launch_dropin_resp(const DropInParams& p, hipStream_t s);
 // General path: per vote, the lane key (L for unknown targets), its index and the packed vote for
 // launch_group_votes.
-hipError_t launch_dropin_keys(const DropInParams& p, uint32_t* keys, uint32_t* vidx, uint32_t* info, hipStream_t s);
+hipError_t launch_dropin_keys(const DropInParams& p, const GroupScratch& g, hipStream_t s);
 
 // AddTargetToReconcile of many nodes' lists (av_add_targets_batch), grouped like the drop-in votes:
 // p.blocks / p.offs / p.entries are launch_group_votes' runs over entries packed by add_word (the
@@ -530,14 +531,12 @@ struct AdmitParams {
 // true: consecutive threads walk a node's touched blocks, then the next node's (the record planes'
 // own order when every block is touched).
 hipError_t launch_admit(const AdmitParams& p, bool lane_major, hipStream_t s);
-// Drop-in batch grouping: stable radix sort of (lane key, position) into (keys_s, perm_s) (keys_t,
-// perm_t: the other buffer set), run-length encoding into lanes / offs (n_runs + 1) / *n_runs, and the
-// (vote index, packed vote) entries in grouped order. scratch: group_votes_scratch_words(n) u64.
+// Drop-in batch grouping over g (batch_layout.h GroupScratch): stable radix sort of (lane key,
+// position) into (keys_s, perm_s) (keys_t, perm_t: the other buffer set), run-length encoding into
+// lanes / offs (runs + 1) / *nruns, and the (vote index, packed vote) entries in grouped order.
+// g.temp: group_votes_scratch_words(n) u64.
 uint64_t group_votes_scratch_words(uint32_t n);
-hipError_t launch_group_votes(uint64_t* scratch, const uint32_t* keys, const uint32_t* vidx, const uint32_t* info,
-                              uint32_t n, int key_bits, uint32_t* keys_s, uint32_t* perm_s, uint32_t* keys_t,
-                              uint32_t* perm_t, uint32_t* lanes, uint32_t* offs, uint32_t* n_runs, uint32_t* entries,
-                              hipStream_t s);
+hipError_t launch_group_votes(const GroupScratch& g, uint32_t n, int key_bits, hipStream_t s);
 
 // ---- catalog.hip: the Hash catalog's device lookup
 // av_register_votes_hashed's lookup-and-pack (and av_catalog_find_device's parity dump): vote v's

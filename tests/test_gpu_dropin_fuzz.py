@@ -162,7 +162,7 @@ def test_register_votes_batch_device_grouping(oracle):
 @pytest.mark.parametrize("seed,n_resp,unsorted", [(5, 200, False), (6, 290, False), (7, 250, True)],
                          ids=["fast", "fast_many", "one_unsorted"])
 def test_register_votes_batch_fast_path(oracle, seed, n_resp, unsorted):
-    """The batch fast path (engine_records.cpp av_register_votes_batch: each
+    """The batch fast path (engine_dropin.cpp av_register_votes_batch: each
     Response's targets strictly ascending — a poll set's order, rule R1 — so
     k_dropin_resp applies each lane's run in place, one workgroup per node,
     its Responses in call order, no grouping) == the oracle's RegisterVotes
