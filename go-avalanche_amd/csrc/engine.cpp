@@ -236,7 +236,7 @@ namespace {
 avk::PlanShape plan_shape(const av_engine* e) {
   return {e->k,      e->BL,         e->N,               e->NL,       e->PS,
           e->capped, e->peer_world, e->comm != nullptr, e->pub_mode, e->any_nopoll,
-          e->lossy(), e->loss_neutral};
+          e->lossy(), e->loss_neutral, e->listed};
 }
 avk::PlanKnobs plan_knobs(const av_engine* e) {
   return {e->kernel,   e->virtual_votes, e->vv_min_bl,     e->count_lazy,     e->k_hi_virtual,
@@ -385,18 +385,21 @@ int exchange_tail(av_engine* e, const avk::RoundParams& p, int nb, hipEvent_t ev
   return AV_OK;
 }
 
+// Why no kernel runs a lossy (R5) or listed (R6) sim round of this engine; `what` names the rule.
+int refuse_round(const av_engine* e, const char* what) {
+  AV_CHECK(!e->capped, AV_ERR_UNSUPPORTED, "%s need M <= 4096 (uncapped)", what);
+  AV_CHECK(e->pub_mode != 2, AV_ERR_UNSUPPORTED, "%s: not with the example responder (responder 2)", what);
+  AV_CHECK(e->peer_world <= 1, AV_ERR_UNSUPPORTED, "%s: not on a peer-push engine", what);
+  return AV_OK;
+}
+
 int launch_one_round(av_engine* e, const uint32_t* replay) {
   AV_TRY(round_checks(e, 1));
   avk::RoundPlan plan = plan_for(e, replay != nullptr);
-  if (plan.unsupported && plan.lossy) {  // rule R5: no kernel runs these with lost Responses
-    AV_CHECK(!e->capped, AV_ERR_UNSUPPORTED,
-             "rounds with lost Responses or unresponsive nodes (av_set_loss, av_set_responding) need M <= 4096 "
-             "(uncapped)");
-    AV_CHECK(e->pub_mode != 2, AV_ERR_UNSUPPORTED,
-             "rounds with lost Responses or unresponsive nodes: not with the example responder (responder 2)");
-    AV_CHECK(e->peer_world <= 1, AV_ERR_UNSUPPORTED,
-             "rounds with lost Responses or unresponsive nodes: not on a peer-push engine");
-  }
+  // rules R6 and R5: no kernel runs these rounds, until the lists are cleared or the loss is off
+  if (plan.unsupported && plan.listed) AV_TRY(refuse_round(e, "rounds over peer lists (av_set_peer_lists)"));
+  if (plan.unsupported && plan.lossy)
+    AV_TRY(refuse_round(e, "rounds with lost Responses or unresponsive nodes (av_set_loss, av_set_responding)"));
   AV_CHECK(!plan.unsupported, AV_ERR_UNSUPPORTED,
            "the example responder and av_set_polling need M <= 4096 (uncapped)");
   AV_TRY(materialize(e, plan.wb_votes || plan.wb_cpreset, false));  // (two passes, votes first)
@@ -451,6 +454,18 @@ int launch_one_round(av_engine* e, const uint32_t* replay) {
       lp.lost = e->lost;
       lp.loss_threshold = e->loss_threshold;
       AV_HIP(avk::launch_round_lossy(lp, e->k, plan.loss_neutral, e->stream));
+      break;
+    }
+    case avk::RoundKernel::Listed: {
+      avk::ListedParams q{};
+      q.l.r = p;
+      q.l.responding = e->any_down ? e->responding.get() : nullptr;
+      q.l.lost = e->lost;
+      q.l.loss_threshold = e->loss_threshold;
+      q.offsets = e->list_offsets;
+      q.list = e->list_peers;
+      q.unsent = e->unsent;
+      AV_HIP(avk::launch_round_listed(q, e->k, plan.loss_neutral, e->stream));
       break;
     }
   }

@@ -294,6 +294,13 @@ struct av_engine {
   bool any_down = false;
   avmem::DevBuf<unsigned long long> lost;       // [kLogShards] lost Responses (av_lost_responses)
   bool lossy() const { return loss_threshold != 0 || any_down; }
+  // per-node peer lists (rule R6; av_set_peer_lists): while `listed` holds, sim rounds run
+  // k_round_listed and the peer dumps draw from the lists. Both arrays are replaced as a pair, after
+  // the stream has drained, so a round already enqueued keeps the lists it was enqueued under.
+  bool listed = false;
+  avmem::DevBuf<uint32_t> list_offsets;         // [NL + 1] into list_peers, by local node
+  avmem::DevBuf<uint32_t> list_peers;           // global ids, strictly ascending per node
+  avmem::DevBuf<unsigned long long> unsent;     // [kLogShards] empty slots (av_unsent_polls)
   // per-local-node Processor.round (processor.go:15,40-42): a field only the
   // caller changes (avalanche_test.go:302); allocated on the first set
   std::vector<int64_t> proc_round;

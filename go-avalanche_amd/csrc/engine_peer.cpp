@@ -299,6 +299,8 @@ int av_peer_init(av_engine* e, int32_t world, int32_t rank, const uint8_t* handl
            "diagnostics option solo_barrier was used on this engine: it cannot join a peer exchange");
   AV_CHECK(!e->lossy(), AV_ERR_UNSUPPORTED,
            "lost Responses or unresponsive nodes (av_set_loss, av_set_responding) on a peer-push engine");
+  // (the need masks are drawn from R1)
+  AV_CHECK(!e->listed, AV_ERR_UNSUPPORTED, "peer lists (av_set_peer_lists) on a peer-push engine");
   AV_CHECK(e->arrive != nullptr, AV_ERR_INVALID_ARG, "call av_peer_handles before av_peer_init");
   for (int r = 0; r < world; ++r) {
     void* ptrs[4] = {e->pref[0], e->pref[1], e->pref[2], e->arrive};
@@ -366,6 +368,7 @@ int av_peer_group_serial(av_engine** engines, int32_t world) {
              "exchange already initialised");
     AV_CHECK(!e->lossy(), AV_ERR_UNSUPPORTED,
              "lost Responses or unresponsive nodes (av_set_loss, av_set_responding) on a peer-push engine");
+    AV_CHECK(!e->listed, AV_ERR_UNSUPPORTED, "peer lists (av_set_peer_lists) on a peer-push engine");
   }
   AV_HIP(hipSetDevice(engines[0]->cfg.device));
   for (int r = 0; r < world; ++r) AV_HIP(hipStreamSynchronize(engines[r]->stream));

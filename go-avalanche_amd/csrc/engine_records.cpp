@@ -1,9 +1,11 @@
 // libavhip.so: record I/O outside a round. Validity, reads and writes of records, preferences and
-// poll sets, polling, loss and responding nodes, the census and the counter queries. The drop-in
+// poll sets, polling, loss and responding nodes, peer lists, the census and the counter queries. The drop-in
 // write batches (added targets, votes) are engine_dropin.cpp's.
 #include <cstring>
+#include <utility>
 
 #include "engine.h"
+#include "peer_list_check.h"
 
 using namespace aveng;
 
@@ -227,9 +229,16 @@ int av_sample_lost(av_engine* e, int64_t round, int64_t n0, int64_t n1, uint8_t*
   if (!n) return AV_OK;
   avmem::DevBuf<uint8_t> s;
   AV_HIP(s.alloc(n));
-  AV_HIP(avk::launch_sample_lost(e->cfg.seed, (uint32_t)e->N, (uint32_t)n0, (uint32_t)n1, (uint32_t)round, e->k,
-                                 e->cfg.peer_mode, e->loss_threshold, e->any_down ? e->responding.get() : nullptr, s,
-                                 e->stream));
+  if (e->listed) {  // R6: the lost mask of the listed draw, 0 in empty slots
+    AV_CHECK(n0 >= e->n0 && n1 <= e->n1, AV_ERR_INVALID_ARG, "an engine with peer lists draws for its own nodes only");
+    AV_HIP(avk::launch_sample_listed(e->cfg.seed, (uint32_t)e->n0, (uint32_t)(n0 - e->n0), (uint32_t)(n1 - e->n0),
+                                     (uint32_t)round, e->k, e->list_offsets, e->list_peers, e->loss_threshold,
+                                     e->any_down ? e->responding.get() : nullptr, nullptr, s, e->stream));
+  } else {
+    AV_HIP(avk::launch_sample_lost(e->cfg.seed, (uint32_t)e->N, (uint32_t)n0, (uint32_t)n1, (uint32_t)round, e->k,
+                                   e->cfg.peer_mode, e->loss_threshold, e->any_down ? e->responding.get() : nullptr, s,
+                                   e->stream));
+  }
   AV_HIP(hipMemcpyAsync(out, s, n, hipMemcpyDeviceToHost, e->stream));
   AV_HIP(hipStreamSynchronize(e->stream));
   return AV_OK;
@@ -239,6 +248,51 @@ int av_lost_responses(av_engine* e, int64_t* out) {
   AV_TRY(counter_query(e, out));
   *out = 0;
   return e->lost ? sum_shards(e, e->lost, out) : AV_OK;
+}
+
+// Rule R6: the Connman of every local node (net.go:11-31), from whose NodesIDs() the reference picks
+// whom to query (processor.go:173-182). Validated on the host (peer_list_check.h: the device indexes
+// by what passes there, with no check of its own), converted to 32-bit and uploaded into fresh
+// buffers, which replace the engine's only once everything has succeeded and the stream has drained.
+int av_set_peer_lists(av_engine* e, const int64_t* offsets, const int64_t* peers) {
+  AV_ENTER(e);
+  if (!offsets) {  // back to the whole network
+    if (e->listed || e->list_offsets) {
+      // rounds enqueued under the lists read them: drained before the buffers are freed
+      AV_HIP(hipStreamSynchronize(e->stream));
+      e->list_offsets.reset();
+      e->list_peers.reset();
+    }
+    e->listed = false;
+    return AV_OK;
+  }
+  AV_CHECK(e->peer_world <= 1, AV_ERR_UNSUPPORTED, "av_set_peer_lists on a peer-push engine");
+  AV_CHECK(e->cfg.peer_mode != AV_PEERS_ROUND_ROBIN, AV_ERR_UNSUPPORTED,
+           "av_set_peer_lists on an engine created with AV_PEERS_ROUND_ROBIN");
+  std::vector<uint32_t> off32, list32;
+  int64_t bad = -1;
+  const avk::PeerListError pe = avk::check_peer_lists(e->N, e->n0, (int64_t)e->NL, offsets, peers, &off32, &list32, &bad);
+  AV_CHECK(pe == avk::PeerListError::Ok, AV_ERR_INVALID_ARG, "av_set_peer_lists: %s (local node %lld)",
+           avk::peer_list_error_text(pe), (long long)bad);
+  avmem::DevBuf<uint32_t> d_off, d_list;
+  AV_HIP(d_off.alloc(off32.size()));
+  AV_HIP(d_list.alloc(list32.size()));
+  if (!e->lost) AV_HIP(e->lost.alloc_zeroed(avk::kLogShards, e->stream));
+  if (!e->unsent) AV_HIP(e->unsent.alloc_zeroed(avk::kLogShards, e->stream));
+  AV_HIP(hipMemcpyAsync(d_off, off32.data(), off32.size() * 4, hipMemcpyHostToDevice, e->stream));
+  if (!list32.empty())
+    AV_HIP(hipMemcpyAsync(d_list, list32.data(), list32.size() * 4, hipMemcpyHostToDevice, e->stream));
+  AV_HIP(hipStreamSynchronize(e->stream));  // (the host vectors go; rounds enqueued earlier are done with the old lists)
+  e->list_offsets = std::move(d_off);
+  e->list_peers = std::move(d_list);
+  e->listed = true;
+  return AV_OK;
+}
+
+int av_unsent_polls(av_engine* e, int64_t* out) {
+  AV_TRY(counter_query(e, out));
+  *out = 0;
+  return e->unsent ? sum_shards(e, e->unsent, out) : AV_OK;
 }
 
 int av_applied_votes(av_engine* e, int64_t* out) {
@@ -391,8 +445,15 @@ int av_sample_peers(av_engine* e, int64_t round, int64_t n0, int64_t n1, int32_t
   if (!n) return AV_OK;
   avmem::DevBuf<uint32_t> s;
   AV_HIP(s.alloc(n));
-  AV_HIP(avk::launch_sample_peers(e->cfg.seed, (uint32_t)e->N, (uint32_t)n0, (uint32_t)n1, (uint32_t)round, e->k,
-                                  e->cfg.peer_mode, s, e->stream));
+  if (e->listed) {  // R6: the listed draw, AV_NO_PEER in empty slots
+    AV_CHECK(n0 >= e->n0 && n1 <= e->n1, AV_ERR_INVALID_ARG, "an engine with peer lists draws for its own nodes only");
+    AV_HIP(avk::launch_sample_listed(e->cfg.seed, (uint32_t)e->n0, (uint32_t)(n0 - e->n0), (uint32_t)(n1 - e->n0),
+                                     (uint32_t)round, e->k, e->list_offsets, e->list_peers, 0u, nullptr,
+                                     reinterpret_cast<int32_t*>(s.get()), nullptr, e->stream));
+  } else {
+    AV_HIP(avk::launch_sample_peers(e->cfg.seed, (uint32_t)e->N, (uint32_t)n0, (uint32_t)n1, (uint32_t)round, e->k,
+                                    e->cfg.peer_mode, s, e->stream));
+  }
   AV_HIP(hipMemcpyAsync(out, s, n * 4, hipMemcpyDeviceToHost, e->stream));
   AV_HIP(hipStreamSynchronize(e->stream));
   return AV_OK;

@@ -432,6 +432,25 @@ hipError_t launch_sample_lost(uint64_t seed, uint32_t n_nodes, uint32_t a, uint3
                               int mode, uint32_t loss_threshold, const uint32_t* responding, uint8_t* out,
                               hipStream_t s);
 
+// ---- round_listed.hip: the round over per-node peer lists (rule R6), uncapped, k <= 16
+// Local node nl polls from list[offsets[nl] .. offsets[nl + 1]) (global ids, strictly ascending, never
+// the node itself; validated on the host, peer_list_check.h): all of them in order where there are at
+// most k, the other slots empty; otherwise the first k distinct indices of R1's candidate stream
+// scaled to the list's length (peer_lists.h). An empty slot registers nothing and is no lost Response;
+// every other slot is lost by R5's rule. The body is k_round_lossy's (round_lossy_body.h).
+struct ListedParams {
+  LossyParams l;            // l.lost is always set; l.responding / l.loss_threshold as under R5
+  const uint32_t* offsets;  // [NL + 1]
+  const uint32_t* list;     // [offsets[NL]]
+  unsigned long long* unsent;  // [kLogShards] empty slots of polling local nodes, once per (node, slot)
+};
+hipError_t launch_round_listed(const ListedParams& p, int k, bool neutral, hipStream_t s);
+// The draw of local nodes [a, b) (global ids n0 + a ..) in `round`: peers_out [b - a][k], -1 in empty
+// slots (av_sample_peers), and / or lost_out [b - a][k] bytes, 0 in empty slots (av_sample_lost)
+hipError_t launch_sample_listed(uint64_t seed, uint32_t n0, uint32_t a, uint32_t b, uint32_t round, int k,
+                                const uint32_t* offsets, const uint32_t* list, uint32_t loss_threshold,
+                                const uint32_t* responding, int32_t* peers_out, uint8_t* lost_out, hipStream_t s);
+
 // ---- round_sweep.hip: the persistent streaming round, uncapped, k <= 8 (k_round_sweep itself and its
 // launcher templates: sweep_kernel.h; this unit compiles k = 8 and forwards every other k)
 // k_round_sweep: `blocks` workgroups of 256 threads sweep the tiles; 0 = one wave per tile.

@@ -14,6 +14,7 @@ enum class RoundKernel : int {
   Node,      // k_round_node (capped, k <= 8)
   FirstGen,  // k_round_fast / k_round_capped (any k; responder variants, non-polling nodes, A/B)
   Lossy,     // k_round_lossy (uncapped, any k): lost Responses and unresponsive nodes (rule R5)
+  Listed,    // k_round_listed (uncapped, any k): per-node peer lists (rule R6), with or without R5
 };
 
 // The sweep kernel's build, as far as the records decide it. The launcher (sweep_kernel.h
@@ -35,6 +36,8 @@ struct PlanShape {
   // threshold above 0 or a node marked not responding); loss_neutral: a lost Response arrives with
   // neutral votes (AV_LOSS_NEUTRAL) instead of not at all
   bool lossy = false, loss_neutral = false;
+  // rule R6 (av_set_peer_lists): every local node polls from its own peer list
+  bool listed = false;
 };
 
 // the options the decision reads (av_set_option)
@@ -50,8 +53,8 @@ struct PlanKnobs {
 };
 
 struct RoundPlan {
-  // responder variant 2 or non-polling nodes on a capped engine, or a lossy round (R5) of a capped
-  // engine, of responder variant 2 or of a peer-push engine: no kernel runs them
+  // responder variant 2 or non-polling nodes on a capped engine, or a lossy (R5) or listed (R6) round
+  // of a capped engine, of responder variant 2 or of a peer-push engine: no kernel runs them
   bool unsupported;
   RoundKernel kernel;
   SweepMode mode;  // kernel == Sweep
@@ -82,6 +85,9 @@ struct RoundPlan {
   bool calm;
   // a sim round under R5 (kernel == Lossy); loss_neutral: its lost Responses shift in consider = 0
   bool lossy, loss_neutral;
+  // a sim round over peer lists (kernel == Listed); lossy / loss_neutral then say whether R5 applies
+  // to its non-empty slots and how
+  bool listed;
 };
 
 struct RecordFacts {
@@ -202,9 +208,9 @@ struct RecordFacts {
     uni_ok[out_buf] = p.uni_rows;
     // (every other kind of round: non-klazy, replay, capped, first-generation, an engine with an exchange)
     nq_ok = p.net_quiet_out;
-    if (p.lossy) {
-      // a skipped Response leaves a record short of 8 new votes, a neutral one shifts in consider = 0
-      // (vote.go:56); the round tags no snapshot buffer
+    if (p.lossy || p.listed) {
+      // a skipped Response or an empty slot leaves a record short of 8 new votes, a neutral Response
+      // shifts in consider = 0 (vote.go:56); the round tags no snapshot buffer
       snapshot_written();
       warm_all = false;
       if (p.loss_neutral) c_monotone = false;
@@ -269,6 +275,22 @@ inline RoundPlan plan_round(const RecordFacts& f, const PlanShape& s, const Plan
     r.loss_neutral = s.loss_neutral;
     r.unsupported = r.unsupported || s.capped || s.pub_mode == 2 || s.peer_world > 1;
     r.kernel = RoundKernel::Lossy;
+    r.mode = SweepMode::Check;
+    r.fresh = r.warm = r.vv = r.vv_uniform = r.klazy = r.kconsume = r.calm = false;
+    r.ref_rows = r.uni_rows = r.net_quiet_out = r.net_quiet_in = false;
+    r.wb_votes = f.v_stale;
+    r.wb_counts = f.k_pend;
+    r.wb_cpreset = f.c_preset;
+  }
+  // R6: a sim round over peer lists runs k_round_listed, planned as R5's round is: on the stored
+  // planes alone, whether or not a Response can be lost as well (loss_neutral only where one can).
+  // Replay rounds ignore the lists.
+  if (s.listed && !replay) {
+    r.listed = true;
+    r.lossy = s.lossy;
+    r.loss_neutral = s.lossy && s.loss_neutral;
+    r.unsupported = r.unsupported || s.capped || s.pub_mode == 2 || s.peer_world > 1;
+    r.kernel = RoundKernel::Listed;
     r.mode = SweepMode::Check;
     r.fresh = r.warm = r.vv = r.vv_uniform = r.klazy = r.kconsume = r.calm = false;
     r.ref_rows = r.uni_rows = r.net_quiet_out = r.net_quiet_in = false;

@@ -167,6 +167,15 @@ class Engine {
   // Whether these nodes answer queries in the batched rounds (av_set_responding); they still poll.
   void SetResponding(const std::vector<NodeID>& nodes, bool responds);
   int64_t LostResponses() const;
+  // The topology of the batched rounds (av_set_peer_lists): connmans[n] is node n's Connman, from
+  // whose NodesIDs() the reference picks whom to query (processor.go:173-182, net.go:25-31); nullptr
+  // = a node that knows nobody. One entry per node. The ids are sorted and deduplicated here; a
+  // Connman that lists its own node or an id outside the network is refused (AV_ERR_INVALID_ARG).
+  // From the next round on a node polls from its list alone; with fewer than k peers the other
+  // slots send nothing (UnsentPolls counts them). ClearConnmans: the whole network again.
+  void SetConnmans(const std::vector<const Connman*>& connmans);
+  void ClearConnmans();
+  int64_t UnsentPolls() const;
   // Batched rounds for every node (the hot path).
   void RunRounds(int32_t rounds);
   int64_t Round() const;

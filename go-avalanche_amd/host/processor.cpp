@@ -133,6 +133,32 @@ int64_t Engine::LostResponses() const {
   return n;
 }
 
+void Engine::SetConnmans(const std::vector<const Connman*>& connmans) {
+  if ((int64_t)connmans.size() != opt_.n_nodes)
+    throw Error(AV_ERR_INVALID_ARG, "SetConnmans: one Connman (or nullptr) per node");
+  std::vector<int64_t> offsets(connmans.size() + 1, 0), peers;
+  for (size_t i = 0; i < connmans.size(); ++i) {
+    if (connmans[i]) {
+      // NodesIDs() is in insertion order and AddNode's caller may repeat an id: sorted and
+      // deduplicated here, as av_set_peer_lists takes strictly ascending lists
+      std::vector<NodeID> ids = connmans[i]->NodesIDs();
+      std::sort(ids.begin(), ids.end());
+      ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+      peers.insert(peers.end(), ids.begin(), ids.end());
+    }
+    offsets[i + 1] = (int64_t)peers.size();
+  }
+  check(av_set_peer_lists(h_, offsets.data(), peers.empty() ? nullptr : peers.data()));
+}
+
+void Engine::ClearConnmans() { check(av_set_peer_lists(h_, nullptr, nullptr)); }
+
+int64_t Engine::UnsentPolls() const {
+  int64_t n = 0;
+  check(av_unsent_polls(h_, &n));
+  return n;
+}
+
 void Engine::RunRounds(int32_t rounds) {
   SyncValidity();
   check(av_run_rounds(h_, rounds));

@@ -33,6 +33,7 @@ STATUS_INVALID, STATUS_REJECTED, STATUS_ACCEPTED, STATUS_FINALIZED = 0, 1, 2, 3
 PEERS_RANDOM, PEERS_ROUND_ROBIN = 0, 1
 INIT_NONE, INIT_REJECTED, INIT_ACCEPTED, INIT_BERNOULLI, INIT_PAIRS = 0, 1, 2, 3, 4
 INIT_GIVEN = 5  # av_admit_targets only: acceptance from the caller's accepted[]
+NO_PEER = -1  # av_sample_peers: an empty slot of a node with fewer than k listed peers (rule R6)
 LOSS_SKIP, LOSS_NEUTRAL = 0, 1  # av_set_loss: a lost Response registers nothing / neutral votes
 ABSENT_WORD = 0xFFFE0000
 FINALIZATION_SCORE = 128
@@ -105,6 +106,7 @@ EXPORTED = [
     "av_catalog_intern", "av_catalog_find", "av_catalog_find_device", "av_catalog_hashes", "av_catalog_retire",
     "av_register_votes_hashed",
     "av_set_loss", "av_set_responding", "av_sample_lost", "av_lost_responses",
+    "av_set_peer_lists", "av_unsent_polls",
 ]
 
 _lib = None
@@ -196,6 +198,8 @@ def lib():
         "av_set_responding": (i32, [_vp, _vp, i64, i32]),
         "av_sample_lost": (i32, [_vp, i64, i64, i64, _vp]),
         "av_lost_responses": (i32, [_vp, P(i64)]),
+        "av_set_peer_lists": (i32, [_vp, _vp, _vp]),
+        "av_unsent_polls": (i32, [_vp, P(i64)]),
     }
     for name, (res, args) in sig.items():
         if name == "av_net_quiet_rounds" and os.environ.get("AVHIP_LIB") and not hasattr(L, name):
@@ -556,6 +560,41 @@ class Engine:
         _check(lib().av_lost_responses(self._h, C.byref(out)))
         return out.value
 
+    def set_peer_lists(self, lists):
+        """The Connman of every local node (rule R6: av_set_peer_lists): lists[i] holds the global ids
+        that local node node_range[0] + i may poll, strictly ascending and without the node itself.
+        From the next round on a node polls from its list alone: all of it where it has at most k
+        entries (the other slots stay empty), else k of it drawn like R1's peers. None clears the
+        lists: every node reaches the whole network again."""
+        if lists is None:
+            _check(lib().av_set_peer_lists(self._h, None, None))
+            return
+        rows = [np.ascontiguousarray(np.atleast_1d(np.asarray(r, np.int64)).reshape(-1)) for r in lists]
+        offs = np.zeros(len(rows) + 1, np.int64)
+        if rows:
+            np.cumsum([r.size for r in rows], out=offs[1:])
+        n_local = self.node_range[1] - self.node_range[0]
+        if len(rows) != n_local:
+            raise ValueError(f"set_peer_lists: {len(rows)} lists for {n_local} local nodes")
+        peers = np.concatenate(rows) if rows and offs[-1] else np.zeros(0, np.int64)
+        self.set_peer_lists_csr(offs, peers)
+
+    def set_peer_lists_csr(self, offsets, peers):
+        """set_peer_lists from the C call's own arrays (for networks too large for a list of lists):
+        int64 offsets[local nodes + 1] into int64 peers."""
+        offs = np.ascontiguousarray(offsets, np.int64)
+        peers = np.ascontiguousarray(peers, np.int64)
+        n_local = self.node_range[1] - self.node_range[0]
+        if offs.ndim != 1 or offs.size != n_local + 1 or peers.ndim != 1 or peers.size != offs[-1]:
+            raise ValueError(f"set_peer_lists_csr: {n_local + 1} offsets, the last one len(peers)")
+        _check(lib().av_set_peer_lists(self._h, _ptr(offs), _ptr(peers) if peers.size else None))
+
+    def unsent_polls(self):
+        """Empty slots of polling local nodes in listed rounds since creation (av_unsent_polls)."""
+        out = C.c_int64(0)
+        _check(lib().av_unsent_polls(self._h, C.byref(out)))
+        return out.value
+
     @property
     def round(self):
         out = C.c_int64(0)
@@ -773,6 +812,8 @@ class Engine:
         return out
 
     def sample_peers(self, rnd, n0=0, n1=None):
+        """The device's peer draw of nodes [n0, n1) in round rnd: int32[n1 - n0, k]. On an engine with
+        peer lists: the listed draw of local nodes, NO_PEER (-1) in empty slots."""
         n1 = self.n_nodes if n1 is None else n1
         out = np.zeros((n1 - n0, self.k), np.int32)
         _check(lib().av_sample_peers(self._h, rnd, n0, n1, _ptr(out)))

@@ -30,7 +30,10 @@
  *                          (main.go:110-137 + responder main.go:168-192,
  *                          peers from getSuitableNodeToQuery processor.go:173-182
  *                          / Connman.NodesIDs net.go:25-31 replaced by
- *                          counter-RNG k-peer sampling)
+ *                          counter-RNG k-peer sampling: over the whole
+ *                          network, or over each node's own peer list)
+ *   av_set_peer_lists   <- Connman.AddNode / NodesIDs            net.go:21-31
+ *                          (every node's Connman in one call; rule R6)
  *   av_fetch_updates    <- the *[]StatusUpdate out-parameter     processor.go:61,111
  *                          (device-side canonical ordering: counting sort by
  *                          (round, node) + per-node (slot, target) layout)
@@ -329,6 +332,50 @@ int av_sample_lost(av_engine* e, int64_t round, int64_t n0, int64_t n1, uint8_t*
 /* Lost Responses of polling local nodes since creation, one per (node, slot). */
 int av_lost_responses(av_engine* e, int64_t* out);
 
+/* ---- per-node peer lists: rounds over a network topology (harness rule R6) ----
+ * In the reference every Processor owns a Connman (net.go:11-31) and picks
+ * whom to query from its NodesIDs() (processor.go:173-182). Without lists
+ * every node can reach every other node (R1). With lists, node n has a list
+ * C(n) of d peers: global ids, strictly ascending, none of them n. In engine
+ * round r its k slots poll as follows.
+ *   d <= k: slot s < d polls C(n)[s]; slots s >= d are empty: no query goes
+ *     out, so nothing registers, shifts, is logged, applied or lost; later
+ *     slots keep their own slot index.
+ *   d > k: R1's candidate stream over the list: blocks x = philox4x32-10(ctr =
+ *     {n, r, blk, 1}, key = seed), blk = 0, 1, ..., each word u = (x[i] * d) >>
+ *     32; the first k distinct u in stream order; slot s polls C(n)[u_s]. A
+ *     list of every other node (N - 1 >= k) draws what AV_PEERS_RANDOM draws.
+ * The draw does not depend on the target: target shards agree with the whole
+ * network. R5 applies to every slot that is not empty (its own draw, or the
+ * listed peer is marked not responding); an empty slot registers nothing in
+ * either loss mode and is no lost Response. A node that does not poll
+ * (av_set_polling) sends nothing; replay rounds ignore the lists. Listed
+ * rounds run a kernel of their own on the stored planes and never take the
+ * settled-round paths. With no lists set the engine plans, launches and
+ * computes what it did before.
+ * On an engine with lists av_sample_peers returns the listed draw with
+ * AV_NO_PEER in empty slots and av_sample_lost 0 there (both for local nodes
+ * only); av_lost_responses and av_applied_votes never count an empty slot.
+ * AV_ERR_UNSUPPORTED: from av_set_peer_lists on a peer-push engine or one
+ * created with AV_PEERS_ROUND_ROBIN, from av_peer_init / av_peer_group_serial
+ * on an engine with lists (the need masks are drawn from R1); from
+ * av_run_rounds, with nothing changed, for a listed round of an engine with
+ * M > 4096 or of responder variant 2 (the engine goes on once the lists are
+ * cleared). RCCL node shards and target shards work. */
+#define AV_NO_PEER (-1)
+/* Connman of every local node (net.go:11-31; processor.go:173-182 reads it): the list of local node
+ * node_begin + i is peers[offsets[i] .. offsets[i+1]), offsets has local_nodes + 1 entries.
+ * offsets == NULL clears the lists (back to the whole network) and frees the
+ * engine's device copy of them, once rounds already enqueued are done. Takes effect
+ * from the next round enqueued. Like av_set_valid, set on every target shard;
+ * a node shard carries the lists of its own nodes, with global peer ids.
+ * AV_ERR_INVALID_ARG, with nothing changed: offsets[0] != 0 or decreasing
+ * offsets, a peer out of range or the node itself, a list not strictly
+ * ascending (the map in net.go:12 holds no duplicate), a total >= 2^31. */
+int av_set_peer_lists(av_engine* e, const int64_t* offsets, const int64_t* peers);
+/* Empty slots of polling local nodes in listed sim rounds since creation, one per (node, slot). */
+int av_unsent_polls(av_engine* e, int64_t* out);
+
 /* ---- outputs ---- */
 int av_updates_count(av_engine* e, int64_t* n);
 /* Whether the device StatusUpdate log overflowed since the last fetch/discard
@@ -494,7 +541,9 @@ int av_read_pref(av_engine* e, int64_t n0, int64_t n1, int64_t t0, int64_t t1, u
 /* Round-start published preference rows of nodes [n0,n1) as stored: [n][BL]
  * u32 bitsets of this engine's target range (bit t % 32 of word t / 32). */
 int av_read_pref_words(av_engine* e, int64_t n0, int64_t n1, uint32_t* out);
-/* Device peer sampling dump: peers of nodes [n0,n1) in round `round`, [n][k]. */
+/* Device peer sampling dump: peers of nodes [n0,n1) in round `round`, [n][k].
+ * With peer lists (av_set_peer_lists): the listed draw of local nodes,
+ * AV_NO_PEER in empty slots. */
 int av_sample_peers(av_engine* e, int64_t round, int64_t n0, int64_t n1, int32_t* out);
 
 /* ---- tuning ----

@@ -5,6 +5,7 @@ per-round kernel throughput.
 
     python tools/run_to_finalization.py --workload c3 [--max-rounds 512] [--json out.json] [--census]
                                         [--loss P] [--loss-mode skip|neutral] [--down F]
+                                        [--degree D | --partition G]
 
 --census adds, per round and from one Engine.census() call over the honest nodes: the targets on
 which no honest node holds a live record, the honest nodes that hold none at all (the example's
@@ -16,6 +17,11 @@ how far the least advanced target's acceptance has got.
 Response does (skip: it never arrives; neutral: it arrives with neutral votes), --down F marks a
 fraction F of the nodes, evenly spread, as not responding (av_set_responding). Defaults: a perfect
 network. The report then carries the lost Responses per round.
+
+--degree D gives every node a random ascending list of D peers to poll from, --partition G splits the
+network into G equal groups with complete lists inside each group (rule R6, av_set_peer_lists;
+tools/topologies.py builds both). The report then carries the unsent polls per round (nodes with
+fewer than k peers); a partitioned network finalizes group by group, each on its own majority.
 """
 import argparse
 import json
@@ -31,6 +37,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402,F401
 
 import avhip  # noqa: E402
+import topologies  # noqa: E402
 from bench import WORKLOADS  # noqa: E402
 
 
@@ -44,6 +51,9 @@ def main():
     ap.add_argument("--loss", type=float, default=0.0, help="probability that a Response is lost")
     ap.add_argument("--loss-mode", default="skip", choices=["skip", "neutral"])
     ap.add_argument("--down", type=float, default=0.0, help="fraction of the nodes that do not respond")
+    topo = ap.add_mutually_exclusive_group()
+    topo.add_argument("--degree", type=int, default=0, help="random peer lists of this many peers per node")
+    topo.add_argument("--partition", type=int, default=0, help="this many equal groups, complete inside")
     args = ap.parse_args()
     n, m, k, init_mode, init_param, byz, replay, desc = WORKLOADS[args.workload]
     assert not replay
@@ -61,6 +71,10 @@ def main():
     n_down = int(args.down * n)
     if n_down:
         e.set_responding(np.arange(n_down, dtype=np.int64) * n // n_down, 0)
+    listed = args.degree > 0 or args.partition > 0
+    if listed:
+        e.set_peer_lists_csr(*(topologies.random_lists(n, args.degree, args.seed & 0xFFFFFFFF) if args.degree
+                               else topologies.group_lists(n, args.partition)))
     honest_records = e.live_records(honest_only=True)
     per_round = []
     t_start = time.perf_counter()
@@ -68,6 +82,7 @@ def main():
     for r in range(args.max_rounds):
         a0, f0 = e.applied_votes(), e.finalized_count()
         l0 = e.lost_responses() if lossy else 0
+        u0 = e.unsent_polls() if listed else 0
         e.set_timing(True)
         e.run_rounds(1)
         ms, _ = e.kernel_stats()
@@ -79,6 +94,8 @@ def main():
                           "finalized": e.finalized_count() - f0, "emitted": emitted, "honest_live": live})
         if lossy:
             per_round[-1]["lost"] = e.lost_responses() - l0
+        if listed:
+            per_round[-1]["unsent"] = e.unsent_polls() - u0
         if args.census:
             c = e.census(honest_only=True, count_sum=False, hist=False)
             tc, nc = c["target_classes"], c["node_classes"]
@@ -105,6 +122,7 @@ def main():
         "applied_votes": total_applied,
         **({"loss": args.loss, "loss_mode": args.loss_mode, "nodes_down": n_down,
             "lost_responses": e.lost_responses()} if lossy else {}),
+        **({"degree": args.degree, "partition": args.partition, "unsent_polls": e.unsent_polls()} if listed else {}),
         "kernel_ms_total": kern,
         "updates_per_s_kernel": total_applied / (kern * 1e-3) if kern else None,
         "wall_s": wall,
